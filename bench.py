@@ -8,9 +8,18 @@
 One "step" = one full training step of the reference's hot loop (phiseg_model.py:194): forward of posterior,
 teacher-forced prior and likelihood, 5 residual cross-entropy + 5 KL terms, backward, TF1 Adam -- for N > 1 plus
 ONE flat gradient all-reduce over RCCL (weak scaling: 64 images per GPU).  Inputs are resident in HBM before the
-timed region.  Rank 0 prints one JSON line; `roofline` times the dominant kernel family (the bf16 MFMA 3x3
-convolutions) with HIP events on the plan's own stream; `cpu_baseline` times the CPU oracle (port of the
-reference's TF1 graph -- TensorFlow 1.12 itself is not installable) on a bounded sample on the host cores.
+timed region.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = milliseconds per timed step).  --dump-outputs DIR then writes, as DIR/<name>.npy, what the timed plan computes
+in the mode it was timed in: for training, one more step of that plan from the model's seeded initial state (the loss and
+the updated weights and moving statistics); for sampling, the last timed pass's output.  Inputs, weights and noise are
+seeded; the default mode's atomics sum in arbitrary order, so two runs agree up to rounding (PHX_DETERMINISTIC=1: bit
+for bit).
+--full adds the measurements that take runs of their own: `roofline` times the dominant kernel family (the bf16 MFMA 3x3
+convolutions) with HIP events on the plan's own stream; `cpu_baseline` times the CPU oracle (port of the reference's TF1
+graph -- TensorFlow 1.12 itself is not installable) on a bounded sample on the host cores; the other BASELINE.json
+workloads and the reference's own loop; for N > 1 the gradient exchange's duration.
 """
 import argparse
 import importlib
@@ -26,6 +35,28 @@ sys.path.insert(0, ROOT)
 F_TRAIN_GFLOP_PER_IMAGE = 75.08       # fwd 25.026 + dgrad + wgrad, live graph, 128x128, 2 classes
 PEAK_BF16_TFLOPS = 2500.0             # MI355X dense bf16 MFMA peak (/opt/skills/guides/MI355X_MICROARCH.md)
 PEAK_F32_TFLOPS = 157.3               # fp32 matrix peak (v_mfma_f32_32x32x2_f32, 64 FLOP/clk/SIMD): the fp32 parity path's roofline
+DUMP_MAX_BYTES = 64 << 20             # --dump-outputs: all files together
+DUMP_SAMPLE = 6 << 20                 # --dump-outputs: an output with more elements is written as a seeded sample of this many
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy, float64 kept, anything else as float32.  An array of more than DUMP_SAMPLE
+    elements is written flattened as the elements at DUMP_SAMPLE fixed indices (seed 0, ascending): the same for every run and build
+    of the same arguments, so two builds compare output for output.  More than DUMP_MAX_BYTES in all: ValueError, nothing written."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.size > DUMP_SAMPLE:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        out[name] = a
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError("--dump-outputs: %d bytes, more than %d" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def make_config(batch, compute_dtype, exp="phiseg_7_5", image_size=128, nlabels=None, norm="batch"):
@@ -241,11 +272,13 @@ def train_api_rate(args, model, steps=10):
 
 
 def self_launch(n):
-    """`python bench.py --gpus N` from a plain shell (no WORLD_SIZE in the environment): become
-    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <argv>`,
-    one rank per GPU; rank 0 prints the one JSON line.  (RCCL refuses two ranks on one device: with fewer GPUs than ranks only
-    PHX_DIST_BACKEND=gloo -- the protocol-test transport -- is accepted.)"""
+    """`python bench.py --gpus N` from a plain shell (no WORLD_SIZE in the environment): run
+    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <argv>`
+    as a child process, one rank per GPU, and exit with its status; rank 0 prints the one JSON line.  (A child, not exec: the
+    device count below initialises the GPU runtime, and a process holding the GPU must not replace its program.)  (RCCL refuses
+    two ranks on one device: with fewer GPUs than ranks only PHX_DIST_BACKEND=gloo -- the protocol-test transport -- is accepted.)"""
     import socket
+    import subprocess
     import torch
     have = torch.cuda.device_count() if torch.cuda.is_available() else 0
     if have < n and os.environ.get("PHX_DIST_BACKEND") != "gloo":
@@ -259,7 +292,8 @@ def self_launch(n):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    rc = subprocess.call(cmd)
+    sys.exit(rc if rc >= 0 else 128 - rc)            # (killed by signal k: the shell's 128 + k)
 
 
 def main():
@@ -269,10 +303,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=64, help="images per GPU")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-other-workloads", action="store_true", help="skip config.other_workloads / train_api_images_per_s")
-    ap.add_argument("--profile-table", action="store_true", help="print the per-layer kernel timing table")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed plan computes as DIR/<name>.npy (training: one more step "
+                         "from the seeded initial state; sampling: the last timed pass)")
+    ap.add_argument("--full", action="store_true",
+                    help="also roofline, cpu_baseline, config.other_workloads / train_api_images_per_s and, for N > 1, the "
+                         "gradient exchange's duration (each measured after the timed steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without roofline")
+    ap.add_argument("--no-other-workloads", action="store_true", help="--full without config.other_workloads / train_api_images_per_s")
+    ap.add_argument("--profile-table", action="store_true", help="--full: print the per-layer kernel timing table")
     # the other BASELINE.json configurations (the default run is config 2, the headline metric):
     ap.add_argument("--exp", default="phiseg_7_5", help="experiment config (phiseg/experiments/*.py), e.g. probunet")
     ap.add_argument("--workload", default="train", choices=["train", "generate"],
@@ -285,8 +325,10 @@ def main():
                     help="generate: Monte-Carlo samples drawn per image in one pass (the prior's x-only encoder is shared); "
                          "0: one sample per image and pass, the reference's call pattern")
     args = ap.parse_args()
+    if args.profile_table and not args.full:
+        ap.error("--profile-table prints the roofline measurement's tables: add --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        self_launch(args.gpus)            # does not return: this process becomes torch.distributed.run
+        self_launch(args.gpus)            # does not return: exits with the status of its torch.distributed.run child
 
     import numpy as np
     import torch
@@ -347,9 +389,30 @@ def main():
     dt = ctx.max_float(dt_own)
     loss = None if generate else float(plan.fetch(model.loss_tot))
     assert plan.barrier_timeouts() == 0, "an in-kernel grid barrier timed out during the timed steps: the result is invalid"
+    if args.dump_outputs:
+        st = sess.store
+        if not generate:
+            # The state after the timed training steps is not reproducible: the default mode's atomics sum in arbitrary order, and
+            # Adam and the training dynamics amplify the last-bit differences over the steps.  So the store goes back to its seeded
+            # initial state (weights, moving statistics, Adam moments, step and noise counter) and the timed plan runs one more step,
+            # in the mode it was timed in (every rank: the step includes the gradient exchange).
+            st.initialize(model.init_seed)
+            torch.cuda.synchronize()              # (torch work; the plan replays on its own streams)
+            step()
+            plan.sync()
+            torch.cuda.synchronize()
+            assert plan.barrier_timeouts() == 0, "an in-kernel grid barrier timed out in the step of --dump-outputs"
+        if ctx.rank == 0:
+            if generate:                          # the last timed pass's soft-max output (sampling never changes the weights)
+                outs = {"output": plan.fetch(plan.fetches[0])}
+            else:                                 # what a caller of the step holds after it: the loss and the updated model
+                outs = {"loss_tot": plan.fetch(model.loss_tot), "params": st.params[:st.n_live]}
+                if st.n_state:
+                    outs["state"] = st.state[:st.n_state]
+            dump_outputs(args.dump_outputs, outs)
     ranks_seen = int(round(ctx.sum_float(1.0)))          # every rank that really took part in the timed collectives
     dp_diag = None
-    if ctx.active and not generate:
+    if args.full and ctx.active and not generate:
         try:
             # after the timed region: what a first multi-GPU run needs to diagnose itself -- every rank's own time for the timed steps and
             # the duration of the gradient exchange (HIP events on the plan's stream around phx_comm_allreduce_sum_f32, ten more steps)
@@ -410,7 +473,7 @@ def main():
         out["config"]["comm"].update(dp_diag)
     if not generate and args.exp == "phiseg_7_5" and args.image_size == 128:
         out["step_tflops"] = images / dt * F_TRAIN_GFLOP_PER_IMAGE / 1e3
-    if ctx.rank == 0 and not args.no_roofline and args.dtype == "bf16":
+    if args.full and ctx.rank == 0 and not args.no_roofline and args.dtype == "bf16":
         rows_all, rows, fam, fl, ms, nl = conv_family(plan)
         if args.profile_table:
             hb = {}
@@ -511,7 +574,7 @@ def main():
                                                  "frac": dom[1][0] / dom[1][1] / 1e9 / PEAK_BF16_TFLOPS}
     headline = (not generate and args.exp == "phiseg_7_5" and args.image_size == 128 and args.norm == "batch" and args.dtype == "bf16"
                 and args.batch == 64)
-    if ctx.rank == 0 and ctx.world == 1 and headline and not args.no_other_workloads:
+    if args.full and ctx.rank == 0 and ctx.world == 1 and headline and not args.no_other_workloads:
         # the other BASELINE.json configurations and the reference's own loop, inside the same invocation (the headline line above is
         # unchanged by them: they run after its timed region)
         # the reference's own loop (sess.run with a host batch and the loss fetched every step, phiseg_model.py:193-194): the like-for-like figure
@@ -523,7 +586,7 @@ def main():
         # what north_star's 1e-4 parity costs: the fp32 path (conv_direct.hip, VALU), the one pinned to the oracle's per-level logits / ELBO
         ow["phiseg_7_5 fp32 parity path, training step"] = side_workload(args, ctx, "phiseg_7_5", "batch", False, steps=10, warmup=2, dtype="f32")
         out["config"]["other_workloads"] = ow
-    if ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline and not generate and args.exp == "phiseg_7_5" \
+    if args.full and ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline and not generate and args.exp == "phiseg_7_5" \
             and args.image_size == 128 and args.norm == "batch":
         out["cpu_baseline"] = cpu_baseline()
         out["cpu_baseline"]["gpu_first_step_loss_same_inputs"] = gpu_first_step_loss(args)

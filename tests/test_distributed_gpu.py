@@ -155,25 +155,40 @@ def test_native_rccl_allreduce_two_devices(tmp_path):
         np.testing.assert_allclose(np.load(str(tmp_path / ("rank%d.npy" % rk))), ref, rtol=1e-6, atol=1e-6)
 
 
-def test_bench_self_launches_its_ranks(tmp_path):
-    """`python bench.py --gpus 2` from a plain shell (no WORLD_SIZE): bench.py re-executes itself under torch.distributed.run with
-    two ranks (here both on the test box's one GPU, gloo carrying the exchange), rank 0 prints the one JSON line, and the line says
-    which transport the timed gradient exchange took and how many ranks took part (config.comm)."""
+def _bench_two_ranks(tmp_path, *flags):
+    """`python bench.py --gpus 2 --batch 4 <flags>` from a plain shell (gloo: both ranks on the test box's one GPU) -> the one line."""
     import json
     env = dict(os.environ, PHX_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONPATH=ROOT)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "2", "--batch", "4",
-           "--no-cpu-baseline", "--no-roofline", "--no-other-workloads"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "2", "--batch", "4"] + list(flags)
     r = subprocess.run(cmd, env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["config"]["global_batch"] == 8 and out["config"]["parallelism"] == "dp2"
-    comm = out["config"]["comm"]
-    assert comm["path"] == "torch_gloo_host_staged" and comm["ranks_seen"] == 2
+    assert out["config"]["comm"]["path"] == "torch_gloo_host_staged" and out["config"]["comm"]["ranks_seen"] == 2
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and np.isfinite(out["config"]["final_loss"])
+    return out
+
+
+def test_bench_self_launches_its_ranks(tmp_path):
+    """`python bench.py --gpus 2` from a plain shell (no WORLD_SIZE): bench.py runs itself under torch.distributed.run as a child with
+    two ranks (here both on the test box's one GPU, gloo carrying the exchange), rank 0 prints the one JSON line, and the line says
+    which transport the timed gradient exchange took and how many ranks took part (config.comm); with --full also the exchange's
+    duration."""
+    comm = _bench_two_ranks(tmp_path, "--full", "--no-cpu-baseline", "--no-roofline", "--no-other-workloads")["config"]["comm"]
     # the line diagnoses a multi-GPU run by itself: the exchange's duration (HIP events around it on the plan's stream) and every rank's own step time
     assert comm["allreduce_ms_median_rank0"] > 0 and comm["allreduce_ms_max_over_ranks"] >= comm["allreduce_ms_median_rank0"] * 0.999
     assert len(comm["ms_per_step_per_rank"]) == 2 and all(v > 0 for v in comm["ms_per_step_per_rank"]) and comm["allreduce_mbytes"] > 1
-    assert out["value"] > 0 and np.isfinite(out["config"]["final_loss"])
+
+
+def test_bench_plain_two_rank_line_and_dump(tmp_path):
+    """The plain data-parallel line (no --full: no exchange diagnostics) and --dump-outputs with two ranks: every rank replays the
+    step from the seeded state (it includes the gradient exchange), rank 0 writes the loss and the updated model."""
+    out = _bench_two_ranks(tmp_path, "--dump-outputs", str(tmp_path / "dump"))
+    assert "allreduce_ms_median_rank0" not in out["config"]["comm"] and "roofline" not in out
+    files = sorted(os.listdir(str(tmp_path / "dump")))
+    assert files == ["loss_tot.npy", "params.npy", "state.npy"], files
+    assert all(np.all(np.isfinite(np.load(str(tmp_path / "dump" / f)))) for f in files)

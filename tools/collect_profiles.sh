@@ -1,14 +1,14 @@
 #!/bin/bash
 # GPU box: the evidence behind bench.py's numbers -> gpurun_out/final/ (copy the summaries into profiles/ afterwards)
 #   PHX_COMMIT=$(git rev-parse --short HEAD) in the gpurun command line: stamped into the summaries (the box has no .git)
-#   1. bench.py (default flags) JSON line + per-layer conv table
+#   1. bench.py --full JSON line + per-layer conv table
 #   2. rocprofv3 --kernel-trace --stats of the same command (rocpd database -> tools/prof_summary.py)
 #   3. rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate passes, kernel trace only (-> tools/pmc_summary.py)
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/final
 mkdir -p $O
 cd $R
-[ -n "$SKIP_BENCH" ] || python bench.py --profile-table > $O/bench.json 2> $O/bench_table.txt
+[ -n "$SKIP_BENCH" ] || python bench.py --full --profile-table > $O/bench.json 2> $O/bench_table.txt
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d $O/stats -- python $R/bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-roofline --no-other-workloads > $O/stats.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
