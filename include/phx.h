@@ -526,6 +526,35 @@ size_t phx_validation_metrics_ws_bytes(int I, int N, int M, int P, int C);
 int phx_validation_metrics(const float* sm, const unsigned char* gt, const unsigned char* sref, void* work, size_t work_bytes,
                            int I, int N, int M, int P, int C, int label0, float* out, void* stream);
 
+/* ---- per-pixel Monte-Carlo sample statistics: the uncertainty / error maps of the inference API (phiseg_model.py:378-475,
+ * phiseg_generate_samples.py:46-82) in one pass over the samples (csrc/mc_stats.hip) -----------------------------------------
+ *   logits, sm [I][N][P][C] f32: the N samples' summed logits / their soft-max (2 <= N <= 1024, 2 <= C <= 8); either may be NULL
+ *   gt   [I][M][P] u8 annotations (1 <= M <= 8; NULL: no E_SY / E_YY), sref [I][P] u8 one annotation (NULL: no XENT_MEAN)
+ *   mean_sm [I][P][C] f32 mean soft-max, amax [I][P] u8 its arg-max (first maximum wins, like np.argmax); both nullable
+ *   maps [I][PHX_MC_NMAPS][P] f32: only the planes whose bit (1u << PHX_MC_*) is set in map_mask are written
+ * With sm_i sample i's soft-max, l_i its logits, m = mean_i sm_i, eps = 1e-8:
+ *   STD_MEAN           mean_c sqrt(var_i sm_i[c]), population variance                       (phiseg_model.py:468-469)
+ *   XENT_MEAN          mean_i (logsumexp(l_i) - l_i[sref])                                   (eval_xent :111, :433-446, :473)
+ *   COV_TRACE          trace of the population covariance over samples of clip(l_i[:C-1], 1e-5, 1 - 1e-5) -- the reference sums
+ *                      the eigenvalues of that matrix; it clips the LOGITS, not the soft-max (:378-403)
+ *   COV_DET            determinant of the unbiased C x C sample covariance of sm_i (:406-430).  Soft-max rows sum to one, so this
+ *                      matrix is singular in exact arithmetic and the value is rounding noise (in the reference as well)
+ *   COV_DET_DROP_LAST  the same on classes 0 .. C-2 (the reference's commented-out line :419): the meaningful determinant
+ *   E_SS               -sum_c m[c] mean_i log(sm_i[c] + eps)                                 (phiseg_generate_samples.py:54-66)
+ *   E_SY               -mean_j mean_i log(sm_i[gt_j] + eps)                                  (:68-73)
+ *   E_YY               -mean_{j<M} mean_{i<M} log(sm_i[gt_j] + eps): the reference's formula, which indexes SAMPLES where it
+ *                      means annotations (:75-80); needs N >= M
+ * A map requested without the input it needs is PHX_E_INVAL.  C = 2 / 4 read one pixel's classes as one 8 / 16 byte word (PHX_E_ALIGN
+ * otherwise).  Second moments are pivot-shifted double sums.  No scratch is needed: the size query returns 0, work may be NULL. */
+enum { PHX_MC_STD_MEAN = 0, PHX_MC_XENT_MEAN = 1, PHX_MC_COV_TRACE = 2, PHX_MC_COV_DET = 3, PHX_MC_COV_DET_DROP_LAST = 4, PHX_MC_E_SS = 5,
+       PHX_MC_E_SY = 6, PHX_MC_E_YY = 7, PHX_MC_NMAPS = 8 };
+size_t phx_mc_stats_ws_bytes(int I, int N, int M, int P, int C);
+int phx_mc_stats(const float* logits, const float* sm, const unsigned char* gt, const unsigned char* sref, int I, int N, int M, int P,
+                 int C, unsigned map_mask, float* mean_sm, unsigned char* amax, float* maps, void* work, size_t work_bytes,
+                 void* stream);
+/* eval_xent (phiseg_model.py:111) of one graph instance: out[p] = logsumexp(logits[p][:]) - logits[p][labels[p]], npix pixels */
+int phx_softmax_xent_map(const float* logits, const unsigned char* labels, float* out, size_t npix, int C, void* stream);
+
 /* ---- transposed convolution (tfwrapper/layers.py:197-258, tf.nn.conv2d_transpose) --------------
  * x [B,H,W,Cin] -> y [B, H*sh, W*sw, Cout], filter w_hwoi [kh][kw][Cout][Cin] fp32 (TF's layout), SAME padding, optional bias and
  * activation.  dgrad: dy [B, H*sh, W*sw, Cout] -> dx [B,H,W,Cin].  wgrad ACCUMULATES into dw_hwoi.  Direct (untuned) kernels: no

@@ -149,8 +149,12 @@ class Plan(ForwardLowering, BackwardLowering):
 
     def __init__(self, store, fetches, loss=None, batch=1, training=True, compute_dtype="f32", optimize=True,
                  rng_seed=42, sample_offset=0, loss_inv_batch=None, stream=None, use_hip_graph=True,
-                 split_optimizer=False, n_lanes=None, stamp_tagged=False):
+                 split_optimizer=False, n_lanes=None, stamp_tagged=False, fed=()):
+        """fed: tensors (latents of z_list) whose values the caller feeds (set_input(tensor, array)) instead of having them computed:
+        the plan does not descend through them, so whatever only served them is not launched."""
         self.L = rt.lib()
+        self.fed = set(fed)
+        assert not self.fed or loss is None, "latent feeds are for inference plans"
         self.store = store
         self.graph = store.graph
         self.B = int(batch)
@@ -388,6 +392,8 @@ class Plan(ForwardLowering, BackwardLowering):
             if op in want:
                 continue
             want.add(op)
+            if self.fed and any(o in self.fed for o in op.outputs):
+                continue                                  # a fed tensor: its producer stays as the feed's place holder, nothing above it
             stack.extend(i.op for i in op.inputs)
         ops = [op for op in self.graph.ops if op in want]
         return self._coarse_first(ops)
@@ -580,6 +586,7 @@ class Plan(ForwardLowering, BackwardLowering):
 
     # ---- execution ------------------------------------------------------------------------------
     def set_input(self, name, array):
+        """name: a placeholder's name ("x_input", "s_input") or a fed tensor (the `fed` argument)."""
         b = self.feeds[name]
         a = np.ascontiguousarray(array, dtype=_NP_DT[b.dt]).reshape(-1)
         assert a.size == b.n, "feed %s: got %d elements, plan expects %d" % (name, a.size, b.n)

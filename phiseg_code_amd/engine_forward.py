@@ -209,7 +209,7 @@ class ForwardLowering:
             sig = sib[0]
             add = None
             for c in mu.outputs[0].consumers:
-                if (c in opset and c.type == "add" and c.inputs[0] is mu.outputs[0] and c.inputs[1].op.type == "mul"
+                if (c in opset and c.type == "add" and c.outputs[0] not in self.fed and c.inputs[0] is mu.outputs[0] and c.inputs[1].op.type == "mul"
                         and c.inputs[1].op.inputs[0] is sig.outputs[0] and c.inputs[1].op.inputs[1].op.type == "random_normal"):
                     add = c
             members = [o for o in (mu, sig, add) if o is not None]
@@ -731,6 +731,14 @@ class ForwardLowering:
                    self.stream)
 
     def _fw_add(self, op, bw):
+        if op.outputs[0] in self.fed:
+            # a fed latent: an F32 feed buffer stands for z, its readers (bilinear up-sampling, the likelihood's first convolutions) read
+            # it like a computed one; mu / sigma / the noise above it are not part of this plan unless something else needs them
+            t = op.outputs[0]
+            z = self._alloc(self._cshape(t), F32, zero=True)
+            self.val[t] = z
+            self.feeds[t] = z
+            return
         mu_t, m = op.inputs
         if m.op.type != "mul" or m.op.inputs[1].op.type != "random_normal":
             raise NotImplementedError("only z = mu + sigma * random_normal(...) is on the hot path")
@@ -819,6 +827,13 @@ class ForwardLowering:
         B, H, W, C = s_out.shape
         self._emit(self.L.residual_ce, sp, None, shp, Ls, None, B, H, W, C, 0.0, 1.0, None, s_out.ptr, sm.ptr,
                    self.stream)
+
+    def _fw_xent_map(self, op, bw):
+        lg, lab = self.val[op.inputs[0]], self.val[op.inputs[1]]
+        assert lg.dt == F32 and lg.shift == 0, "eval_xent reads the summed full-resolution logits"
+        out = self._alloc_like(op.outputs[0])
+        self.val[op.outputs[0]] = out
+        self._emit(self.L.softmax_xent_map, lg.ptr, lab.ptr, out.ptr, out.n, lg.shape[-1], self.stream)
 
     def _fw_kl(self, op, bw):
         mu0, s0, mu1, s1 = [self.val[t] for t in op.inputs]

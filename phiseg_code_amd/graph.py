@@ -364,6 +364,12 @@ def aggregate_logits(s_list):
     return outs[0], outs[1]
 
 
+def softmax_xent_map(logits, labels):
+    """tf.nn.softmax_cross_entropy_with_logits_v2(labels=one_hot(labels), logits=logits) per pixel (eval_xent, phiseg_model.py:111):
+    [B, H, W, C] f32 logits, [B, H, W] u8 labels -> [B, H, W] f32."""
+    return get_default_graph().add_op("xent_map", [logits, labels], {}, [(logits.shape[:-1], KIND_F32)], name="eval_xent")[0]
+
+
 def weighted_sum(scalars, weights):
     return get_default_graph().add_op("weighted_sum", list(scalars), dict(weights=[float(w) for w in weights]),
                                       [((), KIND_F32)], name="loss_tot")[0]

@@ -68,16 +68,79 @@ class Session:
                 engine.device_sync()
         return self.store
 
-    def plan_for(self, fetch_tensors, train, batch, training, stamp_tagged=False):
+    def plan_for(self, fetch_tensors, train, batch, training, stamp_tagged=False, fed=()):
         key = (tuple(id(t) for t in fetch_tensors), bool(train), int(batch), bool(training)) + (("stamped",) if stamp_tagged else ())
+        if fed:
+            key += ("fed",) + tuple(id(t) for t in fed)
         if key not in self.plans:
             store = self._ensure_store()
             world, rank = (self.dist.world, self.dist.rank) if self.dist else (1, 0)
             self.plans[key] = engine.Plan(
                 store, fetch_tensors, loss=self.model.loss_tot if train else None, batch=batch, training=training,
                 compute_dtype=self.compute_dtype, rng_seed=self.rng_seed, sample_offset=rank * batch,
-                loss_inv_batch=1.0 / (batch * world), split_optimizer=bool(self.dist and self.dist.active), stamp_tagged=stamp_tagged)
+                loss_inv_batch=1.0 / (batch * world), split_optimizer=bool(self.dist and self.dist.active), stamp_tagged=stamp_tagged,
+                fed=fed)
         return self.plans[key]
+
+    def latent_feeds(self, feed_dict):
+        """The latent feeds of a feed_dict: keys that are members of model.z_list, in level order (phiseg_model.py:315 of the
+        reference: sess.run(s_out_list, {z_list[i]: ...}) decodes chosen latents).  Any other tensor key that is not a placeholder
+        cannot be fed."""
+        m = self.model
+        fed = []
+        for k in feed_dict:
+            if isinstance(k, G.Tensor) and k is not m.x_inp and k is not m.s_inp:
+                lv = [i for i, z in enumerate(m.z_list) if z is k]
+                if not lv:
+                    raise ValueError("feed_dict: %r is neither a placeholder nor a member of z_list -- only latents can be fed" % (k,))
+                fed.append((lv[0], k))
+        return [k for _, k in sorted(fed, key=lambda e: e[0])]
+
+    def _launch(self, tensors, feed_dict, train=False):
+        """Compile (once) and run the plan of these fetches with these feeds -> the plan; nothing is copied back."""
+        m = self.model
+        fed = self.latent_feeds(feed_dict)
+        if fed and train:
+            raise ValueError("latent feeds are for inference: a training step computes its own posterior samples")
+        x = feed_dict.get(m.x_inp)
+        if x is None:
+            raise ValueError("feed_dict must provide x_inp")
+        x = np.asarray(x)
+        training = bool(feed_dict.get(m.training_pl, False))
+        if train and training and m.bn_double_update:
+            tensors = tensors + [m.s_out_eval]         # Q4: the second graph instances run (and update moving statistics) too
+        plan = self.plan_for(tensors, train, x.shape[0], training, fed=fed)
+        if "x_input" in plan.feeds:                    # (a fully fed decode of a likelihood that does not read x has no use for it)
+            plan.set_input("x_input", x)
+        if "s_input" in plan.feeds:
+            if m.s_inp not in feed_dict:
+                raise ValueError("these fetches need s_inp")
+            plan.set_input("s_input", feed_dict[m.s_inp])
+        for t in fed:
+            want = plan.feeds[t].shape
+            v = np.asarray(feed_dict[t], dtype=np.float32)
+            if tuple(v.shape) != tuple(want):
+                raise ValueError("latent feed %s: got shape %s, the plan expects %s" % (t.name, v.shape, want))
+            plan.set_input(t, v)
+        if m.lr_pl in feed_dict and float(feed_dict[m.lr_pl]) != self._lr:
+            self._lr = float(feed_dict[m.lr_pl])
+            self.store.set_lr(self._lr)               # (synchronises: the plans replay on their own HIP streams)
+        dp = self.dist is not None and self.dist.active
+        if train and dp:
+            plan.run_main()
+            self.dist.allreduce_sum(self.store.grads[:self.store.n_live], plan)
+            plan.run_opt()
+        else:
+            plan.run()
+        return plan
+
+    def run_buffers(self, tensors, feed_dict):
+        """Run the plan of `tensors` and hand back its device buffers instead of host copies: -> (plan, [plan.val[t] ...]).  The
+        buffers belong to the plan and are overwritten by its next run; work on them is enqueued on plan.stream (nothing here
+        synchronises or copies)."""
+        tensors = list(tensors)
+        plan = self._launch(tensors, feed_dict or {})
+        return plan, [plan.val[t] for t in tensors]
 
     def run(self, fetches, feed_dict=None):
         feed_dict = feed_dict or {}
@@ -93,29 +156,8 @@ class Session:
         spec = walk([fetches] if single else list(fetches))
         train = any(isinstance(f, TrainStep) for f in flat)
         tensors = [f for f in flat if isinstance(f, G.Tensor)]
-        x = feed_dict.get(m.x_inp)
-        if x is None:
-            raise ValueError("feed_dict must provide x_inp")
-        x = np.asarray(x)
-        training = bool(feed_dict.get(m.training_pl, False))
-        if train and training and m.bn_double_update:
-            tensors = tensors + [m.s_out_eval]         # Q4: the second graph instances run (and update moving statistics) too
-        plan = self.plan_for(tensors, train, x.shape[0], training)
-        plan.set_input("x_input", x)
-        if "s_input" in plan.feeds:
-            if m.s_inp not in feed_dict:
-                raise ValueError("these fetches need s_inp")
-            plan.set_input("s_input", feed_dict[m.s_inp])
-        if m.lr_pl in feed_dict and float(feed_dict[m.lr_pl]) != self._lr:
-            self._lr = float(feed_dict[m.lr_pl])
-            self.store.set_lr(self._lr)               # (synchronises: the plans replay on their own HIP streams)
+        plan = self._launch(tensors, feed_dict, train)
         dp = self.dist is not None and self.dist.active
-        if train and dp:
-            plan.run_main()
-            self.dist.allreduce_sum(self.store.grads[:self.store.n_live], plan)
-            plan.run_opt()
-        else:
-            plan.run()
         vals = [plan.fetch(f) if isinstance(f, G.Tensor) else None for f in flat]
         if dp and "s_input" in plan.feeds:
             # the loss kernels scale every term by 1 / (B_local * world): a rank's scalar is its SHARE of the global-batch mean
@@ -203,6 +245,7 @@ class phiseg():
         self.train_step = TrainStep(self.loss_tot)
 
         self._multi = {}
+        self._lazy = {}                                   # graph nodes added after construction (eval_xent, ...): see _lazy_node
         self.keep_checkpoint_every_n_hours = 3.0          # tf.train.Saver(max_to_keep=1, keep_checkpoint_every_n_hours=3) (phiseg_model.py:144)
         self._ckpt_permanent, self._ckpt_last_permanent = {}, time.time()
         self._ckpt_written, self._ckpt_order = {}, {}      # per saver prefix: the steps this instance wrote (set / in write order)
@@ -581,6 +624,130 @@ class phiseg():
             e = [np.exp(v - v.max(axis=-1, keepdims=True)) for v in lv]
             return [v / v.sum(axis=-1, keepdims=True) for v in e]
         return lv
+
+    # ---- graph nodes the reference builds in __init__ and this class adds on first use, as sampling_graph does: __init__'s graph,
+    # its op order and the plans compiled from it stay exactly as they are for everyone who never asks for these ------------------
+    def _lazy_node(self, name, build):
+        if name not in self._lazy:
+            G.set_default_graph(self.graph)
+            self._lazy[name] = build()
+        return self._lazy[name]
+
+    @property
+    def eval_xent(self):
+        """tf.nn.softmax_cross_entropy_with_logits_v2(labels=s_inp_oh, logits=s_out_eval) (phiseg_model.py:111): [B, X, Y]"""
+        return self._lazy_node("eval_xent", lambda: G.softmax_xent_map(self.s_out_eval, self.s_inp))
+
+    @property
+    def s_out_eval_sm_list(self):
+        """softmax of every level of s_out_eval_list (phiseg_model.py:100-102)"""
+        return self._lazy_node("s_out_eval_sm_list", lambda: [G.aggregate_logits([t])[1] for t in self.s_out_eval_list])
+
+    def _s_out_sum(self):
+        """_aggregate_output_list(s_out_list) without labels: self.s_out is an output of the loss operator and needs s_inp."""
+        return self._lazy_node("s_out_sum", lambda: G.aggregate_logits(self.s_out_list)[0])
+
+    # ---- latents in, latents out (phiseg_model.py:313-322, 478-502) ---------------------------------------------------------------
+    def generate_samples_from_z(self, z_list, x_in, output_all_levels=False):
+        """Decode chosen latents: z_list[l] is fed for level l ([B, h_l, w_l, zdim]); a shorter list (or None entries) leaves the
+        remaining levels to the posterior, which then needs s_inp -- use sess.run with a feed_dict for that."""
+        fd = {t: d for t, d in zip(self.z_list, z_list) if d is not None}
+        fd[self.training_pl] = False
+        fd[self.x_inp] = x_in
+        if output_all_levels:
+            return self.sess.run(self.s_out_list, feed_dict=fd)
+        return self.sess.run(self._s_out_sum(), feed_dict=fd)
+
+    def generate_samples_from_prior(self, x_in, output_all_levels=False):
+        """(The reference passes output_all_levels in the x_in slot of generate_samples_from_z, SURVEY.md Q8: fixed here.)"""
+        z_samples = self.generate_prior_samples(x_in)
+        out = self.generate_samples_from_z(z_samples, x_in, output_all_levels)
+        self._advance_noise()
+        return out
+
+    def generate_posterior_samples(self, x_in, s_in, return_params=False):
+        fd = {self.training_pl: False, self.x_inp: x_in, self.s_inp: s_in}
+        if return_params:            # one run: mu and sigma are the parameters of the very samples returned
+            out = tuple(self.sess.run([self.z_list, self.mu_list, self.sigma_list], feed_dict=fd))
+        else:
+            out = self.sess.run(self.z_list, feed_dict=fd)
+        self._advance_noise()
+        return out
+
+    def generate_all_output_levels(self, x_in, s_in=None):
+        """s_out_list is the likelihood of POSTERIOR samples: it needs s_inp, which the reference's method forgets to feed."""
+        fd = {self.x_inp: x_in, self.training_pl: False}
+        if s_in is not None:
+            fd[self.s_inp] = s_in
+        y_list = self.sess.run(self.s_out_list, feed_dict=fd)
+        self._advance_noise()
+        return y_list
+
+    # ---- Monte-Carlo uncertainty / error maps (phiseg_model.py:378-475): one sampling pass, maps formed on the device ---------------
+    def _mc_maps(self, x_in, num_samples, maps, s_gt=None, amax=False):
+        """Draw num_samples segmentations per image in ONE pass (sampling_graph where the prior shares an x-only encoder, x tiled to
+        batch B * num_samples on s_out_eval otherwise: inference-mode normalisation makes the rows independent), hand the plan's
+        device buffers to phx_mc_stats on the plan's stream and copy back only the maps.  -> (dict name -> [B, X, Y], arg-max of
+        the mean soft-max [B, X, Y] or None).  Advances the noise step once."""
+        import torch
+        from phiseg_code_amd import uncertainty as unc
+        n = int(num_samples)
+        if n < 2 or n > 1024:
+            raise ValueError("num_samples must be 2 .. 1024 (got %d)" % n)
+        x = np.asarray(x_in)
+        B = x.shape[0]
+        if getattr(self.exp_config.prior, '__name__', '') == 'phiseg':
+            lg_t, sm_t = self.sampling_graph(n)
+        else:
+            lg_t, sm_t = self.s_out_eval, self.s_out_eval_sm
+            x = np.repeat(x, n, axis=0)                                        # rows b * n + k, as sampling_graph lays them out
+        need_lg = any(m in ("xent_mean", "cov_trace") for m in maps)
+        need_sm = amax or any(m not in ("xent_mean", "cov_trace") for m in maps)
+        tensors = ([lg_t] if need_lg else []) + ([sm_t] if need_sm else [])
+        plan, bufs = self.sess.run_buffers(tensors, {self.training_pl: False, self.x_inp: x})
+        lg = bufs[0] if need_lg else None
+        sm = bufs[-1] if need_sm else None
+        X, Y, C = (lg or sm).shape[1:]
+        sref = None
+        if s_gt is not None:
+            sref = torch.as_tensor(np.ascontiguousarray(np.asarray(s_gt).reshape((B, X, Y)), dtype=np.uint8)).to((lg or sm).t.device)
+            torch.cuda.current_stream().synchronize()                          # uploaded on torch's stream, read on the plan's
+        out, _, amax_t = unc.mc_stats_device(lg.ptr if lg else None, sm.ptr if sm else None, None, sref.data_ptr() if sref is not None else None,
+                                             B, n, 0, X * Y, C, list(maps), plan.stream, amax=amax)
+        plan.sync()
+        res = {m: out[:, unc.PLANE[m]].cpu().numpy().reshape((B, X, Y)) for m in maps}
+        am = amax_t.cpu().numpy().reshape((B, X, Y)) if amax else None
+        self._advance_noise()
+        return res, am
+
+    @staticmethod
+    def _per_image(a):
+        """The reference squeezes the batch axis of a single image: [1, X, Y] -> [X, Y]; B > 1 keeps [B, X, Y] (an extension)."""
+        return a[0] if a.shape[0] == 1 else a
+
+    def predict_segmentation_sample_variance_sm_cov(self, x_in, num_samples):
+        """phiseg_model.py:378-403: the sum of the eigenvalues (= trace) of the covariance over the samples of the clipped LOGITS of
+        all classes but the last."""
+        res, _ = self._mc_maps(x_in, num_samples, ("cov_trace",))
+        return self._per_image(res["cov_trace"])
+
+    def predict_segmentation_sample_variance_sm_cov_bf(self, x_in, num_samples, drop_last_class=False):
+        """phiseg_model.py:406-430: determinant of the unbiased sample covariance of the soft-max.  With every class in it that
+        matrix is singular (rows sum to one) and the value is rounding noise, in the reference too; drop_last_class=True is the
+        reference's commented-out line 419 and gives the meaningful determinant."""
+        name = "cov_det_drop_last" if drop_last_class else "cov_det"
+        res, _ = self._mc_maps(x_in, num_samples, (name,))
+        return self._per_image(res[name])
+
+    def get_crossentropy_error_map(self, s_gt, x_in, num_samples=100):
+        """phiseg_model.py:433-446: mean over the samples of eval_xent -> [B, X, Y] (the reference does not squeeze this one)."""
+        res, _ = self._mc_maps(x_in, num_samples, ("xent_mean",), s_gt=s_gt)
+        return res["xent_mean"]
+
+    def predict_mean_variance_and_error_maps(self, s_gt, x_in, num_samples):
+        """phiseg_model.py:449-475 -> (arg-max of the mean soft-max, mean over classes of the per-pixel std, mean eval_xent)."""
+        res, am = self._mc_maps(x_in, num_samples, ("std_mean", "xent_mean"), s_gt=s_gt, amax=True)
+        return self._per_image(am.astype(np.int64)), self._per_image(res["std_mean"]), self._per_image(res["xent_mean"])
 
     def _advance_noise(self):
         """Every sampling call must see fresh noise (TF's stateful RNG): bump the Philox step word."""
