@@ -498,6 +498,14 @@ int phx_kl_diag_gauss_multi(const void* const* ptrs, const size_t* n, const floa
  * the flat parameter arena.  grad_scale multiplies g first (1/world for averaged all-reduce). */
 int phx_adam_tf1(float* p, const float* g, float* m, float* v, size_t n, const float* lr_dev, float beta1,
                  float beta2, float eps, const int32_t* step_dev, void* stream);
+/* tf.train.MomentumOptimizer (phiseg_model.py:137-138), TF 1.12 ApplyMomentum:
+ *   accum = momentum * accum + g
+ *   p -= use_nesterov ? lr * g + lr * momentum * accum      (the NEW accum)
+ *                     : lr * accum
+ * One launch over the flat arena; lr is read on the device (graph replay picks up a new value).  g is read-only; p, g and accum
+ * must be 16-byte aligned (PHX_E_ALIGN) and non-null (PHX_E_INVAL).  The step counter stays with phx_step_increment. */
+int phx_momentum_tf1(float* p, const float* g, float* accum, size_t n, const float* lr_dev,
+                     float momentum, int use_nesterov, void* stream);
 int phx_step_increment(int32_t* step_dev, void* stream);
 /* diagnostic: *dst_u64 = the device's constant-rate (100 MHz) wall clock when the stream reaches this point; the engine
  * (PHX_STAMPS=1) brackets every operator with these to draw the per-lane timeline of a replayed plan without a profiler

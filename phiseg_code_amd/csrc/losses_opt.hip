@@ -1,4 +1,4 @@
-// Reparameterisation sampler, residual multinoulli (cross-entropy) loss, hierarchical KL, TF1 Adam.
+// Reparameterisation sampler, residual multinoulli (cross-entropy) loss, hierarchical KL, TF1 Adam and Momentum.
 #include "philox.h"
 #include "phx_common.h"
 
@@ -305,6 +305,32 @@ __global__ void k_adam_tf1(float* __restrict__ p, const float* __restrict__ g, f
     }
 }
 
+// ---- Momentum, TF 1.12 ApplyMomentum (tf.train.MomentumOptimizer) ----------------------------------
+// accum = momentum * accum + g;  p -= NESTEROV ? lr * g + lr * momentum * accum (the new accum) : lr * accum.
+// NESTEROV is a template parameter: the branch is resolved at launch, not per element.
+template <bool NESTEROV>
+__device__ __forceinline__ void momentum_update(float& p, float g, float& a, float lr, float mom) {
+    a = mom * a + g;
+    p -= NESTEROV ? lr * g + lr * mom * a : lr * a;
+}
+template <bool NESTEROV>
+__global__ void k_momentum_tf1(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ accum, size_t n4,
+                               size_t n, const float* __restrict__ lr_dev, float mom) {
+    const float lr = *lr_dev;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+        float4 pp = reinterpret_cast<float4*>(p)[i], gg = reinterpret_cast<const float4*>(g)[i];
+        float4 aa = reinterpret_cast<float4*>(accum)[i];
+        float* P = &pp.x; const float* Gp = &gg.x; float* A = &aa.x;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) momentum_update<NESTEROV>(P[j], Gp[j], A[j], lr, mom);
+        reinterpret_cast<float4*>(p)[i] = pp;
+        reinterpret_cast<float4*>(accum)[i] = aa;
+    }
+    // tail
+    const size_t i = n4 * 4 + blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i < n) momentum_update<NESTEROV>(p[i], g[i], accum[i], lr, mom);
+}
+
 __global__ void k_step_increment(int32_t* s) { *s += 1; }
 __global__ void k_stamp(unsigned long long* dst) { *dst = wall_clock64(); }      // constant 100 MHz counter
 __global__ void k_sum_scalars(const float* in, int n, float* out) {
@@ -456,6 +482,20 @@ int phx_adam_tf1(float* p, const float* g, float* m, float* v, size_t n, const f
     int grid = phx_grid_for(n4 > 0 ? n4 : 1, 256, 8192);
     hipLaunchKernelGGL(k_adam_tf1, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, n, lr_dev, beta1, beta2,
                        eps, step_dev);
+    PHX_CHECK_LAUNCH();
+    return PHX_OK;
+}
+int phx_momentum_tf1(float* p, const float* g, float* accum, size_t n, const float* lr_dev, float momentum, int use_nesterov,
+                     void* stream) {
+    PHX_REQUIRE(p && g && accum && lr_dev, PHX_E_INVAL, "momentum: null argument");
+    PHX_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)accum) & 15) == 0, PHX_E_ALIGN,
+                "momentum: arenas must be 16-byte aligned");
+    const size_t n4 = n / 4;
+    int grid = phx_grid_for(n4 > 0 ? n4 : 1, 256, 8192);
+    if (use_nesterov)
+        hipLaunchKernelGGL(k_momentum_tf1<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, accum, n4, n, lr_dev, momentum);
+    else
+        hipLaunchKernelGGL(k_momentum_tf1<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, accum, n4, n, lr_dev, momentum);
     PHX_CHECK_LAUNCH();
     return PHX_OK;
 }

@@ -3,10 +3,10 @@
 This is the run-time half of the TF1 replacement: where the reference calls
 ``sess.run([train_step, loss_tot], feed_dict)`` (phiseg/phiseg_model.py:194) this module
 
-* keeps all variables in flat fp32 device arenas (parameters, gradients, Adam m / v) so the optimiser and
+* keeps all variables in flat fp32 device arenas (parameters, gradients, the optimiser's slots: Adam m / v or the Momentum accumulator) so the optimiser and
   the data-parallel gradient all-reduce are single flat operations (``ParamStore``);
 * compiles (fetches, loss) for one batch size / training flag into a list of libphx launches: forward of
-  the live graph, reverse-mode backward (Appendix C of SURVEY.md), TF1 Adam (``Plan``);
+  the live graph, reverse-mode backward (Appendix C of SURVEY.md), the TF1 optimiser update -- Adam or Momentum (``Plan``);
 * captures the list into a hipGraph and replays it per step (device-side step counter / learning rate, so a
   replay needs no host-side argument patching).
 
@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from phiseg_code_amd import graph as G
+from phiseg_code_amd import optimizers
 from phiseg_code_amd import runtime as rt
 from phiseg_code_amd.tfwrapper import normalisation as tfnorm
 
@@ -33,8 +34,10 @@ from phiseg_code_amd.engine_forward import ForwardLowering
 class ParamStore:
     """Flat arenas for every variable of a graph (created once, shared by all plans of a model)."""
 
-    def __init__(self, graph, seed=0, live=None):
-        """live: names of the trainable variables the loss depends on (live_variables()).  They are laid out FIRST, so the
+    def __init__(self, graph, seed=0, live=None, optimizer=None):
+        """optimizer: the optimizers.AdamOptimizer / MomentumOptimizer instance whose slots the store keeps (None: Adam).  Adam has
+        two slot arenas (adam_m, adam_v), Momentum one (accum); the arenas of the other optimiser are None.
+        live: names of the trainable variables the loss depends on (live_variables()).  They are laid out FIRST, so the
         data-parallel exchange sums grads[:n_live] only -- the never-consumed up-sampling branches of the reference's zoo
         (887 808 parameters) get no gradient and need no reduction."""
         self.graph = graph
@@ -60,8 +63,14 @@ class ParamStore:
         dev = _device()
         self.params = torch.zeros(max(off, 4), dtype=torch.float32, device=dev)
         self.grads = torch.zeros_like(self.params)
-        self.adam_m = torch.zeros_like(self.params)
-        self.adam_v = torch.zeros_like(self.params)
+        self.optimizer = optimizer
+        self.slot_names = optimizers.slot_names(optimizer)          # TF's slot names, in the order of slot_arenas()
+        self.adam_m = self.adam_v = self.accum = None
+        if self.slot_names == ('Momentum',):
+            self.accum = torch.zeros_like(self.params)
+        else:
+            self.adam_m = torch.zeros_like(self.params)
+            self.adam_v = torch.zeros_like(self.params)
         self.state = torch.zeros(max(soff, 4), dtype=torch.float32, device=dev)
         self.step = torch.zeros(1, dtype=torch.int32, device=dev)          # optimiser step t-1 (also the noise step)
         self.noise_step = torch.zeros(1, dtype=torch.int32, device=dev)    # Philox step word of sampling plans
@@ -71,9 +80,13 @@ class ParamStore:
     def initialize(self, seed=0):
         """tf.global_variables_initializer() (phiseg_model.py:175)."""
         self.load({name: v.initial_value(seed) for name, v in self.graph.variables.items()})
-        self.adam_m.zero_()
-        self.adam_v.zero_()
+        for arena in self.slot_arenas():
+            arena.zero_()
         self.step.zero_()
+
+    def slot_arenas(self):
+        """The device arenas of the optimiser's slots, in the order of slot_names: [adam_m, adam_v] or [accum]."""
+        return [self.accum] if self.accum is not None else [self.adam_m, self.adam_v]
 
     def _slot(self, name):
         v = self.graph.variables[name]
@@ -117,6 +130,7 @@ class ParamStore:
 
     def export_adam(self):
         """-> {variable name: (m, v)} for the trainable variables (TF's '<var>/Adam', '<var>/Adam_1' slots)."""
+        assert self.adam_m is not None, "export_adam: this store keeps the slots %s (export_slots())" % (self.slot_names,)
         torch.cuda.synchronize()
         out = {}
         for name, v in self.graph.variables.items():
@@ -127,6 +141,7 @@ class ParamStore:
         return out
 
     def load_adam(self, slots):
+        assert self.adam_m is not None, "load_adam: this store keeps the slots %s (load_slots())" % (self.slot_names,)
         for name, (m, vv) in slots.items():
             v = self.graph.variables.get(name)
             if v is None or not v.trainable:
@@ -138,9 +153,38 @@ class ParamStore:
                 arena[off:off + v.size] = a.to(arena.device)
         torch.cuda.synchronize()
 
+    def export_slots(self):
+        """-> {variable name: {slot name: array}} for the trainable variables; slot names are TF's: 'Adam' (m) and 'Adam_1' (v),
+        or 'Momentum' (the accumulator)."""
+        torch.cuda.synchronize()
+        out = {}
+        for name, v in self.graph.variables.items():
+            if v.trainable:
+                off = self.offset[name]
+                out[name] = {sn: arena[off:off + v.size].cpu().numpy().reshape(v.shape)
+                             for sn, arena in zip(self.slot_names, self.slot_arenas())}
+        return out
+
+    def load_slots(self, slots):
+        """slots: {variable name: {slot name: array}} (export_slots()).  Variables the graph does not train are skipped; a slot name
+        this store's optimiser does not keep is an error."""
+        arenas = dict(zip(self.slot_names, self.slot_arenas()))
+        for name, per_var in slots.items():
+            v = self.graph.variables.get(name)
+            if v is None or not v.trainable:
+                continue
+            off = self.offset[name]
+            for sn, val in per_var.items():
+                if sn not in arenas:
+                    raise ValueError("load_slots: the store keeps the slots %s, not '%s' (variable %s)" % (self.slot_names, sn, name))
+                a = torch.as_tensor(np.asarray(val, dtype=np.float32).reshape(-1))
+                assert a.numel() == v.size, "shape mismatch for the %s slot of %s" % (sn, name)
+                arenas[sn][off:off + v.size] = a.to(arenas[sn].device)
+        torch.cuda.synchronize()
+
     def reset_optimizer(self):
-        self.adam_m.zero_()
-        self.adam_v.zero_()
+        for arena in self.slot_arenas():
+            arena.zero_()
         self.set_step(0)
 
 
@@ -149,8 +193,10 @@ class Plan(ForwardLowering, BackwardLowering):
 
     def __init__(self, store, fetches, loss=None, batch=1, training=True, compute_dtype="f32", optimize=True,
                  rng_seed=42, sample_offset=0, loss_inv_batch=None, stream=None, use_hip_graph=True,
-                 split_optimizer=False, n_lanes=None, stamp_tagged=False, fed=()):
-        """fed: tensors (latents of z_list) whose values the caller feeds (set_input(tensor, array)) instead of having them computed:
+                 split_optimizer=False, n_lanes=None, stamp_tagged=False, fed=(), optimizer=None):
+        """optimizer: the optimizers.AdamOptimizer / MomentumOptimizer instance the update is lowered from (None: Adam with TF's
+        defaults); its slots must be the ones `store` keeps.
+        fed: tensors (latents of z_list) whose values the caller feeds (set_input(tensor, array)) instead of having them computed:
         the plan does not descend through them, so whatever only served them is not launched."""
         self.L = rt.lib()
         self.fed = set(fed)
@@ -165,7 +211,11 @@ class Plan(ForwardLowering, BackwardLowering):
         self.inv_batch = float(loss_inv_batch) if loss_inv_batch is not None else 1.0 / self.B
         self.loss = loss
         self.optimize = bool(optimize and loss is not None)
-        self.split_optimizer = split_optimizer      # data-parallel: [fwd+bwd] | all-reduce | [adam]
+        self.optimizer = optimizer
+        if self.optimize and optimizers.slot_names(optimizer) != store.slot_names:
+            raise ValueError("Plan: the optimizer needs the slots %s, the store keeps %s -- build the ParamStore with the same optimizer"
+                             % (optimizers.slot_names(optimizer), store.slot_names))
+        self.split_optimizer = split_optimizer      # data-parallel: [fwd+bwd] | all-reduce | [optimiser]
         self.use_hip_graph = use_hip_graph and os.environ.get("PHX_HIP_GRAPH", "1") == "1"     # 0: replay the launch list on the lane streams
         # Lanes: independent sub-graphs (posterior / prior encoders, the per-level likelihood chains) are enqueued on
         # separate HIP streams so the many small-map kernels overlap; cross-lane dependencies are HIP events.  The
@@ -572,9 +622,13 @@ class Plan(ForwardLowering, BackwardLowering):
             if self.split_optimizer:
                 self._cur = self.opt_launches
             s = self.store
-            self._emit(self.L.adam_tf1, s.params.data_ptr(), s.grads.data_ptr(), s.adam_m.data_ptr(),
-                       s.adam_v.data_ptr(), s.n_train, s.lr.data_ptr(), 0.9, 0.999, 1e-8, s.step.data_ptr(),
-                       self.stream)
+            if isinstance(self.optimizer, optimizers.MomentumOptimizer):
+                self._emit(self.L.momentum_tf1, s.params.data_ptr(), s.grads.data_ptr(), s.accum.data_ptr(), s.n_train,
+                           s.lr.data_ptr(), float(self.optimizer.momentum), int(bool(self.optimizer.use_nesterov)), self.stream)
+            else:
+                self._emit(self.L.adam_tf1, s.params.data_ptr(), s.grads.data_ptr(), s.adam_m.data_ptr(),
+                           s.adam_v.data_ptr(), s.n_train, s.lr.data_ptr(), 0.9, 0.999, 1e-8, s.step.data_ptr(),
+                           self.stream)
             self._emit(self.L.step_increment, s.step.data_ptr(), self.stream)
             self._cur = self.launches
 
@@ -635,7 +689,7 @@ class Plan(ForwardLowering, BackwardLowering):
             self.sync()
 
     def run_main(self):
-        """Data-parallel use: forward+backward only (graph 1); run_opt() applies Adam after the all-reduce."""
+        """Data-parallel use: forward+backward only (graph 1); run_opt() applies the optimiser after the all-reduce."""
         if not self.use_hip_graph or not getattr(self, "_warm", False):
             self._run_list(self.launches)
             self._warm = True

@@ -102,7 +102,7 @@ class ForwardLowering:
         return c
 
     def _packed(self, W):
-        """bf16 packed copies of a 3x3 filter, refreshed at the head of every run (after Adam moved W)."""
+        """bf16 packed copies of a 3x3 filter, refreshed at the head of every run (after the optimiser moved W)."""
         if W.name not in self._wpk:
             kh, kw, cin, cout = W.shape
             wf, wd = self._alloc((9 * cin * cout,), BF16), self._alloc((9 * cin * cout,), BF16)

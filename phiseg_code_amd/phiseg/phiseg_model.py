@@ -22,6 +22,7 @@ import numpy as np
 
 from phiseg_code_amd import engine
 from phiseg_code_amd import graph as G
+from phiseg_code_amd import optimizers
 from phiseg_code_amd import utils
 
 logging.basicConfig(level=logging.INFO, format='%(asctime)s %(message)s')
@@ -38,7 +39,7 @@ class _Flag:
 
 
 class TrainStep:
-    """Handle returned as ``model.train_step``: fetching it runs backward + Adam (optimizer.minimize)."""
+    """Handle returned as ``model.train_step``: fetching it runs backward + the optimiser's update (optimizer.minimize)."""
 
     def __init__(self, loss):
         self.loss = loss
@@ -59,7 +60,7 @@ class Session:
     def _ensure_store(self):
         if self.store is None:
             self.store = engine.ParamStore(self.model.graph, seed=self.model.init_seed,
-                                           live=engine.live_variables(self.model.loss_tot))
+                                           live=engine.live_variables(self.model.loss_tot), optimizer=self.model.optimizer)
             if self.dist is not None and self.dist.active:
                 # identical replicas (the Philox initialiser already gives every rank the same values; this also covers
                 # weights loaded on one rank only)
@@ -79,7 +80,7 @@ class Session:
                 store, fetch_tensors, loss=self.model.loss_tot if train else None, batch=batch, training=training,
                 compute_dtype=self.compute_dtype, rng_seed=self.rng_seed, sample_offset=rank * batch,
                 loss_inv_batch=1.0 / (batch * world), split_optimizer=bool(self.dist and self.dist.active), stamp_tagged=stamp_tagged,
-                fed=fed)
+                fed=fed, optimizer=self.model.optimizer)
         return self.plans[key]
 
     def latent_feeds(self, feed_dict):
@@ -242,6 +243,7 @@ class phiseg():
             weights.append(1.0)
         self.loss_tot = G.weighted_sum(terms, weights)
         self.loss_dict['total_loss'] = self.loss_tot
+        self.optimizer = self._make_optimizer(exp_config)
         self.train_step = TrainStep(self.loss_tot)
 
         self._multi = {}
@@ -254,6 +256,22 @@ class phiseg():
 
     def checks(self):
         pass
+
+    def _make_optimizer(self, exp_config):
+        """phiseg_model.py:135-141: Momentum is instantiated with momentum 0.9 and Nesterov's form, anything else with the learning
+        rate alone.  A config without `optimizer` trains with Adam.  The instance only carries hyper-parameters (engine.Plan lowers
+        it to phx_adam_tf1 / phx_momentum_tf1), so it has to be an AdamOptimizer or a MomentumOptimizer (or a subclass of one)."""
+        opt = getattr(exp_config, 'optimizer', optimizers.AdamOptimizer)
+        known = (optimizers.AdamOptimizer, optimizers.MomentumOptimizer)
+        if not callable(opt) or (isinstance(opt, type) and not issubclass(opt, known)):
+            raise ValueError("exp_config.optimizer must be optimizers.AdamOptimizer or optimizers.MomentumOptimizer (or a subclass), got %r" % (opt,))
+        if opt == optimizers.MomentumOptimizer:
+            optimizer = opt(learning_rate=self.lr_pl, momentum=0.9, use_nesterov=True)
+        else:
+            optimizer = opt(learning_rate=self.lr_pl)
+        if not isinstance(optimizer, known):
+            raise ValueError("exp_config.optimizer produced %r: neither an AdamOptimizer nor a MomentumOptimizer" % (optimizer,))
+        return optimizer
 
     # ---- training loop (phiseg_model.py:166-207) -------------------------------------------------
     def _is_writer(self):
@@ -457,31 +475,33 @@ class phiseg():
         return getattr(self.exp_config, 'checkpoint_format', 'npz')
 
     def save_weights(self, path, format='npz', keep_prefix=None, max_to_keep=0, average_state=True):
-        """What tf.train.Saver writes for this graph (phiseg_model.py:144-148, 534-535): every variable, the Adam slots under
-        TF's names '<var>/Adam' (m) and '<var>/Adam_1' (v), and the step (TF keeps beta1_power / beta2_power and global_step;
-        one integer carries the same information).  File: <path>.npz, or with format='tf' a TensorFlow tensor-bundle checkpoint
-        <path>.index + <path>.data-00000-of-00001 (tfwrapper/tf_checkpoint.py) that tf.train.Saver.restore of the reference
-        graph accepts: same variable names, beta1_power / beta2_power / global_step included.  Data-parallel: batch-norm
-        moving statistics are averaged over the replicas first (per-replica statistics); rank 0 writes."""
+        """What tf.train.Saver writes for this graph (phiseg_model.py:144-148, 534-535): every variable, the optimiser's slots under
+        TF's names -- '<var>/Adam' (m) and '<var>/Adam_1' (v) for Adam, '<var>/Momentum' (the accumulator) for Momentum -- and the
+        step (TF keeps beta1_power / beta2_power and global_step; one integer carries the same information).  File: <path>.npz, or
+        with format='tf' a TensorFlow tensor-bundle checkpoint <path>.index + <path>.data-00000-of-00001
+        (tfwrapper/tf_checkpoint.py) that tf.train.Saver.restore of the reference graph accepts: same variable names and
+        global_step, with beta1_power / beta2_power for Adam (TF's MomentumOptimizer has no non-slot variables).  Data-parallel:
+        batch-norm moving statistics are averaged over the replicas first (per-replica statistics); rank 0
+        writes."""
         store = self.sess._ensure_store()
         if average_state:              # (a collective: every rank must call save_weights -- _do_validation averages once itself)
             self._average_replica_state()
         if not self._is_writer():
             return
         blob = dict(store.export())
-        for name, (m, v) in store.export_adam().items():
-            blob[name + '/Adam'] = m
-            blob[name + '/Adam_1'] = v
+        for name, per_var in store.export_slots().items():
+            for slot, val in per_var.items():
+                blob[name + '/' + slot] = val
         step = int(store.step.cpu().numpy()[0])
         if format == 'tf':
-            from phiseg_code_amd import optimizers
             from phiseg_code_amd.tfwrapper import tf_checkpoint
             if path.endswith('.npz'):
                 path = path[:-4]
-            # TF 1.x AdamOptimizer's non-slot variables: beta_power = beta^(t + 1) after t updates; minimize() counts global_step
-            b1, b2 = optimizers.AdamOptimizer.beta1, optimizers.AdamOptimizer.beta2
-            blob['beta1_power'] = np.asarray(b1 ** (step + 1), dtype=np.float32)
-            blob['beta2_power'] = np.asarray(b2 ** (step + 1), dtype=np.float32)
+            if store.adam_m is not None:
+                # TF 1.x AdamOptimizer's non-slot variables: beta_power = beta^(t + 1) after t updates; minimize() counts global_step
+                b1, b2 = optimizers.AdamOptimizer.beta1, optimizers.AdamOptimizer.beta2
+                blob['beta1_power'] = np.asarray(b1 ** (step + 1), dtype=np.float32)
+                blob['beta2_power'] = np.asarray(b2 ** (step + 1), dtype=np.float32)
             blob['global_step'] = np.asarray(step, dtype=np.int64)
             tf_checkpoint.write(path, blob)
             d = os.path.dirname(os.path.abspath(path))
@@ -504,8 +524,9 @@ class phiseg():
 
     def load_weights(self, log_dir=None, type='latest', **kwargs):
         """phiseg_model.py:505-525 (+ 'best_ncc', which the reference writes but cannot load -- SURVEY.md Q9).  `log_dir` may
-        also be a checkpoint file / prefix.  Restores variables, Adam slots and the step; a checkpoint without Adam slots
-        (weights only) resets the optimiser state and the step.  A prefix with a `.index` file next to it is a TensorFlow
+        also be a checkpoint file / prefix.  Restores variables, the slots of the model's own optimiser ('<var>/Adam' + '<var>/Adam_1'
+        or '<var>/Momentum') and the step; a checkpoint without them -- weights only, or written under the other optimiser -- loads
+        the variables, resets the optimiser state and the step, and logs one warning.  A prefix with a `.index` file next to it is a TensorFlow
         tensor-bundle checkpoint -- one written by the reference's tf.train.Saver or by save_weights(format='tf') -- and is
         read directly (tfwrapper/tf_checkpoint.py); variables the checkpoint lacks keep their values, as Saver.restore of a
         sub-graph would."""
@@ -528,7 +549,6 @@ class phiseg():
         store = self.sess._ensure_store()
         names = set(self.graph.variables)
         if os.path.exists(path + '.index') and not os.path.exists(path + '.npz'):
-            from phiseg_code_amd import optimizers
             from phiseg_code_amd.tfwrapper import tf_checkpoint
             ck = tf_checkpoint.read(path)
             files = list(ck)
@@ -550,15 +570,23 @@ class phiseg():
             logging.warning('load_weights: %d of %d graph variables are not in %s and keep their values (first: %s)',
                             len(missing), len(names), path, ', '.join(missing[:3]))
         self.last_load_missing = missing
-        slots = {k[:-len('/Adam')]: (ck[k], ck[k + '_1']) for k in files if k.endswith('/Adam') and k + '_1' in files}
+        fset = set(files)
+        slots = {}
+        for name, v in self.graph.variables.items():
+            if v.trainable and all(name + '/' + sn in fset for sn in store.slot_names):
+                slots[name] = {sn: ck[name + '/' + sn] for sn in store.slot_names}
         if slots:
-            store.load_adam(slots)
+            store.load_slots(slots)
             store.set_step(step)
         else:
+            other = [sn for sn in ('Adam', 'Momentum') if sn not in store.slot_names and any(k.endswith('/' + sn) for k in files)]
+            want = ' + '.join("'<var>/%s'" % sn for sn in store.slot_names)
+            logging.warning('load_weights: %s holds %s, not the %s slots of this model\'s optimiser: weights only -- the optimiser '
+                            'state and the step are reset', path, "'<var>/%s' slots" % other[0] if other else 'no optimiser slots', want)
             store.reset_optimizer()
         self.sess._lr = None
         if self.dist is not None and self.dist.active:
-            for t in (store.params, store.state, store.adam_m, store.adam_v):
+            for t in [store.params, store.state] + store.slot_arenas():
                 self.dist.broadcast_(t)
             engine.device_sync()
 
