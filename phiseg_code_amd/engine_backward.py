@@ -2,15 +2,11 @@
 turn the gradient of the operator's outputs into gradients of its inputs and variables -- what `optimizer.minimize` derives in the
 reference (phiseg/phiseg_model.py:135-141) -- plus the gradient bookkeeping (`_add_grad`, `_finalize_grad`)."""
 import ctypes
-import os
 
 import numpy as np
-import torch
 
-from phiseg_code_amd import graph as G
 from phiseg_code_amd import runtime as rt
 from phiseg_code_amd import upconv
-from phiseg_code_amd.tfwrapper import normalisation as tfnorm
 from phiseg_code_amd.engine_common import *  # noqa: F401,F403
 from phiseg_code_amd.engine_common import _BN_SMALL, _BN_SMALL_F32, _BN_WIDE, _BN_WIDE_MAXLINES, _DETERMINISTIC, _NREP, _NREP_MINP, _fgn_mode, _dual_enabled, _noop, _device, _TORCH_DT, _NP_DT, _ESIZE, _LIK_SIDE_MAXLVL, _WGRAD_DEFER_BLOCKS, _STAMPS  # noqa: F401
 
@@ -96,7 +92,7 @@ class BackwardLowering:
         if _BN_WIDE < 2 or xin in self.fetches or self.act_dt != BF16:
             return False
         prod = self._real_producer(xin)
-        if prod is None or prod.type != "conv_unit" or not (self.saved.get(prod) or {}).get("bn_wide") or prod.outputs[0] is not xin:
+        if prod is None or prod.type != "conv_unit" or getattr(self.saved.get(prod), "route", None) is not NormRoute.BN_WIDE or prod.outputs[0] is not xin:
             return False
         if self.op_lane.get(prod) != self.op_lane.get(op):
             return False
@@ -221,31 +217,41 @@ class BackwardLowering:
             else:
                 self._add_grad(t, write_fn=lambda g: self._emit(self.L.memcpy_d2d, g.ptr, d.ptr, d.nbytes, self.stream))
 
+    def _norm_bwd(self, sv, nv, dA, dY, C, act, nrep, sums2, bias=None, tagged=False, s2d=()):
+        """Generic normalisation backward: the reduction over (dA, y), then the fused apply that writes dY and adds dgamma / dbeta.
+        bias: (forward sums, forward pivot, db) pointers of the closed-form conv-bias gradient (phx_norm_bwd_apply_fused_bias and the
+        _s2d / _head forms), None without.  s2d: (h, w) of a phase-form unit, whose hi-res dA is read through the space-to-depth
+        permutation.  A HeadGrad dA is formed on the fly (dy_head w_head^T)."""
+        Lb, y = self.L, sv.y
+        if isinstance(dA, HeadGrad):
+            lead, nb, ydt = (dA.dy.ptr, dA.w_ptr, dA.nout, y.ptr), 0, ()
+            reduce, apply = Lb.norm_bwd_reduce_head, Lb.norm_bwd_apply_fused_head
+        else:
+            lead, nb, ydt = (dA.ptr, dA.dt, y.ptr, y.dt), dA.nbytes, (dY.dt,)
+            reduce, apply = (Lb.norm_bwd_reduce_s2d, Lb.norm_bwd_apply_fused_s2d) if s2d else \
+                (Lb.norm_bwd_reduce, Lb.norm_bwd_apply_fused if bias is None else Lb.norm_bwd_apply_fused_bias)
+        lead += (sv.scale.ptr, sv.shift.ptr, sv.mean.ptr, sv.rstd.ptr)
+        dims = (sv.NS, sv.P, C, sv.G, act, nrep, *s2d, self.stream)
+        self._emit(reduce, *lead, sums2.ptr, *dims, tag="bytes_norm_bwd_reduce" if tagged else None, flops=float(nb + y.nbytes))
+        self._emit(apply, *lead, self.store.ptr(nv["gamma"]), sums2.ptr, dY.ptr, *ydt, self.store.grad_ptr(nv["gamma"]),
+                   self.store.grad_ptr(nv["beta"]), *(bias or ()), *dims,
+                   tag="bytes_norm_bwd_apply" if tagged else None, flops=float(nb + y.nbytes + dY.nbytes))
+
     def _bw_norm_act(self, op):
         a, sv = op.attrs, self.saved[op]
         dA = self.grad[op.outputs[0]]
         act = rt.ACT_CODES[a["act"]]
-        S, Lb = self.stream, self.L
-        if sv["norm"] is None:
-            out = sv["out"]
-            self._add_grad(op.inputs[0], write_fn=lambda g: self._emit(Lb.act_bwd, dA.ptr, dA.dt, out.ptr, out.dt, g.ptr, g.dt, dA.n,
-                                                                       act, S))
+        if sv.norm is None:
+            out = sv.out
+            self._add_grad(op.inputs[0], write_fn=lambda g: self._emit(self.L.act_bwd, dA.ptr, dA.dt, out.ptr, out.dt, g.ptr, g.dt, dA.n,
+                                                                       act, self.stream))
             return
-        if sv.get("inference"):
+        if sv.route is NormRoute.INFER:
             raise NotImplementedError("backward through inference-mode batch norm is not on the hot path")
-        nv = a["norm_vars"]
-        y, NS, P, Gn = sv["y"], sv["NS"], sv["P"], sv["G"]
-        C = y.shape[3]
-        nrep = _NREP if P >= _NREP_MINP else 1
-        sums2 = self._alloc_zeroed(nrep * NS * C * 2)
-
-        def wr(g):
-            self._emit(Lb.norm_bwd_reduce, dA.ptr, dA.dt, y.ptr, y.dt, sv["scale"].ptr, sv["shift"].ptr, sv["mean"].ptr,
-                       sv["rstd"].ptr, sums2.ptr, NS, P, C, Gn, act, nrep, S)
-            self._emit(Lb.norm_bwd_apply_fused, dA.ptr, dA.dt, y.ptr, y.dt, sv["scale"].ptr, sv["shift"].ptr, sv["mean"].ptr,
-                       sv["rstd"].ptr, self.store.ptr(nv["gamma"]), sums2.ptr, g.ptr, g.dt, self.store.grad_ptr(nv["gamma"]),
-                       self.store.grad_ptr(nv["beta"]), NS, P, C, Gn, act, nrep, S)
-        self._add_grad(op.inputs[0], write_fn=wr)
+        C = sv.y.shape[3]
+        nrep = _NREP if sv.P >= _NREP_MINP else 1
+        sums2 = self._alloc_zeroed(nrep * sv.NS * C * 2)
+        self._add_grad(op.inputs[0], write_fn=lambda g: self._norm_bwd(sv, a["norm_vars"], dA, g, C, act, nrep, sums2))
 
     def _bw_flatten(self, op):
         x, d = self.val[op.inputs[0]], self.grad[op.outputs[0]]
@@ -277,235 +283,157 @@ class BackwardLowering:
             self.stream))
 
     def _bw_conv_unit(self, op):
+        """Norm backward (by the saved route) -> dY, then the filter gradient, then the data gradient; the phase-form, general and
+        transposed units have their own gradient methods."""
         if op in self._lat:
             return self._bw_latent_group(self._lat[op])
-        a, sv = op.attrs, self.saved[op]
-        dA = self.grad[op.outputs[0]]
-        x, out = sv["x"], sv["out"]
-        W, b = a["W"], a["b"]
-        k, cin, cout = a["ksize"], W.shape[-2], W.shape[-1]
-        if sv.get("transposed") is not None:
-            cout, cin = W.shape[2], W.shape[3]
-        B, H, Wd = x.shape[0], x.shape[1], x.shape[2]
-        act = rt.ACT_CODES[a["act"]]
-        S, Lb = self.stream, self.L
-        db_done = False
-        upc = sv.get("upconv")
-        if upc is not None:
+        sv, b = self.saved[op], op.attrs["b"]
+        dY, db_done = self._bw_unit_norm(op, sv, self.grad[op.outputs[0]])
+        db = self.store.grad_ptr(b) if (b is not None and not db_done) else None
+        if sv.upconv is not None:
+            return self._bw_unit_upconv(op, sv, dY, db)
+        if sv.general is not None:
+            return self._bw_unit_general(op, sv, dY, db)
+        if sv.transposed is not None:
+            return self._bw_unit_transposed(op, sv, dY, db)
+        self._bw_unit_filter(op, sv, dY, db)
+        self._bw_unit_data(op, sv, dY)
+
+    @staticmethod
+    def _unit_dims(op, sv):
+        """(B, H, W, Cin, Cout) of a unit's convolution, from its saved input and its filter."""
+        W = op.attrs["W"]
+        cin, cout = (W.shape[3], W.shape[2]) if sv.transposed is not None else (W.shape[-2], W.shape[-1])
+        return sv.x.shape[0], sv.x.shape[1], sv.x.shape[2], cin, cout
+
+    # ---- stage 1: the normalisation / activation backward, dA -> (dY, bias gradient already formed?) ------------------------------
+    def _bw_unit_norm(self, op, sv, dA):
+        act = rt.ACT_CODES[op.attrs["act"]]
+        if sv.upconv is not None:
             # phase form (upconv.py): y and everything downstream of it live in the PACKED pixel order; dA is a hi-res map -- the two
             # norm-backward passes read it through the space-to-depth permutation
-            assert isinstance(dA, Buf) and dA.dt == BF16 and not sv.get("bn_small") and not sv.get("norm_small")
-        if sv["norm"] is not None:
-            if "y" not in sv or "mean" not in sv or (sv["norm"] == "batch" and not self.training):
-                raise NotImplementedError("backward through inference-mode batch norm is not on the hot path")
-            nv = a["norm_vars"]
-            y, NS, P, Gn = sv["y"], sv["NS"], sv["P"], sv["G"]
-            if sv.get("bn_wide") and dA.dt == BF16:
-                dY = self._alloc(y.shape, BF16)
-                sg = dA if isinstance(dA, SliceGrad) else None      # the consumer's split-K data gradient left its slices: summed here
-                self._emit(Lb.bn_wide_bwd, None if sg is not None else dA.ptr, sg.ws.ptr if sg is not None else None,
-                           sg.nz if sg is not None else 0, y.ptr, sv["scale"].ptr, sv["shift"].ptr, sv["mean"].ptr, sv["rstd"].ptr,
-                           self.store.ptr(nv["gamma"]), dY.ptr, self.store.grad_ptr(nv["gamma"]),
-                           self.store.grad_ptr(nv["beta"]), P, cout, act, S,
-                           tag="bytes_norm_bwd_apply", flops=float(dY.nbytes + y.nbytes + dY.nbytes))
-            elif sv.get("bn_small") and dA.dt == BF16:
-                dY = self._alloc(y.shape, BF16)
-                self._emit(Lb.bn_small_bwd, dA.ptr, y.ptr, y.dt, sv["scale"].ptr, sv["shift"].ptr, sv["mean"].ptr, sv["rstd"].ptr,
-                           self.store.ptr(nv["gamma"]), dY.ptr, self.store.grad_ptr(nv["gamma"]),
-                           self.store.grad_ptr(nv["beta"]), P, cout, act, S,
-                           tag="bytes_norm_bwd_apply", flops=float(dA.nbytes + y.nbytes + dY.nbytes))
-            elif sv.get("norm_small") and dA.dt == BF16:
-                dY = self._alloc(y.shape, y.dt)
-                self._emit(Lb.norm_small_bwd, dA.ptr, y.ptr, sv["scale"].ptr, sv["shift"].ptr, sv["mean"].ptr, sv["rstd"].ptr,
-                           self.store.ptr(nv["gamma"]), dY.ptr, self.store.grad_ptr(nv["gamma"]),
-                           self.store.grad_ptr(nv["beta"]), self.store.grad_ptr(b) if b is not None else None,
-                           NS, P, cout, Gn, act, S,
-                           tag="bytes_norm_bwd_apply", flops=float(dA.nbytes + y.nbytes + dY.nbytes))
-                db_done = True
-            else:
-                nrep = _NREP if P >= _NREP_MINP else 1   # replicated accumulators: see k_norm_bwd_reduce
-                if _DETERMINISTIC and P >= _NREP_MINP:
-                    nrep = 64                             # one block per replica there: more replicas = more blocks
-                sums2 = self._alloc_zeroed(nrep * NS * cout * 2)
-                Sg = self._alloc((NS * Gn * 2,), F32)
-                dY = self._alloc(y.shape, y.dt)
-                hg = dA if isinstance(dA, HeadGrad) else None
-                fs0 = sv.get("fsums") if b is not None else None
-                onepass = False
-                if (upc is None and hg is None and fs0 is None and sv["norm"] == "batch" and NS == 1 and Gn == cout and isinstance(dA, Buf)
-                        and dA.dt == BF16 and y.dt == BF16 and _onepass_enabled() and Lb.bn_bwd_onepass_supported(P, cout, act)):
-                    # mid-size batch-norm layers: ONE launch, (dA, y) read once and held in registers across a grid barrier
-                    bar = self._alloc_zeroed(int(Lb.bn_bwd_onepass_barrier_words()))
-                    self._barriers.append(bar)
-                    onepass = True
-                    self._emit(Lb.bn_bwd_onepass, dA.ptr, y.ptr, sv["scale"].ptr, sv["shift"].ptr, sv["mean"].ptr, sv["rstd"].ptr,
-                               self.store.ptr(nv["gamma"]), sums2.ptr, bar.ptr, dY.ptr, self.store.grad_ptr(nv["gamma"]),
-                               self.store.grad_ptr(nv["beta"]), P, cout, act, nrep, S,
-                               tag="bytes_norm_bwd_onepass", flops=float(dA.nbytes + y.nbytes + dY.nbytes))
-                elif upc is not None:
-                    self._emit(Lb.norm_bwd_reduce_s2d, dA.ptr, dA.dt, y.ptr, y.dt, sv["scale"].ptr, sv["shift"].ptr, sv["mean"].ptr,
-                               sv["rstd"].ptr, sums2.ptr, NS, P, cout, Gn, act, nrep, H // 2, Wd // 2, S,
-                               tag="bytes_norm_bwd_reduce", flops=float(dA.nbytes + y.nbytes))
-                elif hg is not None:
-                    self._emit(Lb.norm_bwd_reduce_head, hg.dy.ptr, hg.w_ptr, hg.nout, y.ptr, sv["scale"].ptr, sv["shift"].ptr,
-                               sv["mean"].ptr, sv["rstd"].ptr, sums2.ptr, NS, P, cout, Gn, act, nrep, S,
-                               tag="bytes_norm_bwd_reduce", flops=float(y.nbytes))
-                else:
-                    self._emit(Lb.norm_bwd_reduce, dA.ptr, dA.dt, y.ptr, y.dt, sv["scale"].ptr, sv["shift"].ptr,
-                               sv["mean"].ptr, sv["rstd"].ptr, sums2.ptr, NS, P, cout, Gn, act, nrep, S,
-                               tag="bytes_norm_bwd_reduce", flops=float(dA.nbytes + y.nbytes))
-                # group / instance norm keep the convolution bias: its gradient (the per-channel sum of dY) comes out of this
-                # launch in closed form instead of a pass over dY (phx_norm_bwd_apply_fused_bias)
-                fs = sv.get("fsums") if b is not None else None
-                if fs is not None:
-                    db_done = True
-                if onepass:
-                    pass                                  # (the one launch above formed dY, dgamma and dbeta)
-                elif upc is not None:
-                    self._emit(Lb.norm_bwd_apply_fused_s2d, dA.ptr, dA.dt, y.ptr, y.dt, sv["scale"].ptr, sv["shift"].ptr, sv["mean"].ptr,
-                               sv["rstd"].ptr, self.store.ptr(nv["gamma"]), sums2.ptr, dY.ptr, dY.dt, self.store.grad_ptr(nv["gamma"]),
-                               self.store.grad_ptr(nv["beta"]), fs.ptr if fs is not None else None,
-                               sv["fpivot"].ptr if (fs is not None and sv.get("fpivot") is not None) else None,
-                               self.store.grad_ptr(b) if fs is not None else None, NS, P, cout, Gn, act, nrep, H // 2, Wd // 2, S,
-                               tag="bytes_norm_bwd_apply", flops=float(dA.nbytes + y.nbytes + dY.nbytes))
-                elif hg is not None:
-                    self._emit(Lb.norm_bwd_apply_fused_head, hg.dy.ptr, hg.w_ptr, hg.nout, y.ptr, sv["scale"].ptr, sv["shift"].ptr,
-                               sv["mean"].ptr, sv["rstd"].ptr, self.store.ptr(nv["gamma"]), sums2.ptr, dY.ptr,
-                               self.store.grad_ptr(nv["gamma"]), self.store.grad_ptr(nv["beta"]),
-                               fs.ptr if fs is not None else None,
-                               sv["fpivot"].ptr if (fs is not None and sv.get("fpivot") is not None) else None,
-                               self.store.grad_ptr(b) if fs is not None else None, NS, P, cout, Gn, act, nrep, S,
-                               tag="bytes_norm_bwd_apply", flops=float(y.nbytes + dY.nbytes))
-                else:
-                    self._emit(Lb.norm_bwd_apply_fused_bias, dA.ptr, dA.dt, y.ptr, y.dt, sv["scale"].ptr, sv["shift"].ptr,
-                               sv["mean"].ptr, sv["rstd"].ptr, self.store.ptr(nv["gamma"]), sums2.ptr, dY.ptr, dY.dt,
-                               self.store.grad_ptr(nv["gamma"]), self.store.grad_ptr(nv["beta"]),
-                               fs.ptr if fs is not None else None,
-                               sv["fpivot"].ptr if (fs is not None and sv.get("fpivot") is not None) else None,
-                               self.store.grad_ptr(b) if fs is not None else None, NS, P, cout, Gn, act, nrep, S,
-                               tag="bytes_norm_bwd_apply", flops=float(dA.nbytes + y.nbytes + dY.nbytes))
-        elif act != rt.ACT_ID:
-            dY = self._alloc(out.shape, dA.dt)
-            self._emit(Lb.act_bwd, dA.ptr, dA.dt, out.ptr, out.dt, dY.ptr, dY.dt, dA.n, act, S)
+            assert isinstance(dA, Buf) and dA.dt == BF16 and sv.route is NormRoute.GENERIC
+        if sv.norm is None:
+            if act == rt.ACT_ID:
+                return dA, False
+            dY = self._alloc(sv.out.shape, dA.dt)
+            self._emit(self.L.act_bwd, dA.ptr, dA.dt, sv.out.ptr, sv.out.dt, dY.ptr, dY.dt, dA.n, act, self.stream)
+            return dY, False
+        if sv.y is None or sv.mean is None or (sv.norm == "batch" and not self.training):
+            raise NotImplementedError("backward through inference-mode batch norm is not on the hot path")
+        R = NormRoute
+        one_launch = {R.BN_WIDE: self._bw_norm_bn_wide, R.BN_SMALL_F32Y: self._bw_norm_bn_small, R.BN_SMALL: self._bw_norm_bn_small,
+                      R.FGN: self._bw_norm_small, R.NORM_SMALL: self._bw_norm_small}.get(sv.route) if dA.dt == BF16 else None
+        return (one_launch or self._bw_norm_generic)(op, sv, dA, act)
+
+    def _bw_one_launch_args(self, op, sv, dY):
+        """(saved statistics..., gamma, dY, dgamma, dbeta): the argument run the one-launch norm backward kernels share."""
+        nv = op.attrs["norm_vars"]
+        return (sv.scale.ptr, sv.shift.ptr, sv.mean.ptr, sv.rstd.ptr, self.store.ptr(nv["gamma"]), dY.ptr, self.store.grad_ptr(nv["gamma"]),
+                self.store.grad_ptr(nv["beta"]))
+
+    def _bw_norm_bn_wide(self, op, sv, dA, act):
+        y, dY = sv.y, self._alloc(sv.y.shape, BF16)
+        sg = dA if isinstance(dA, SliceGrad) else None      # the consumer's split-K data gradient left its slices: summed here
+        self._emit(self.L.bn_wide_bwd, None if sg is not None else dA.ptr, sg.ws.ptr if sg is not None else None,
+                   sg.nz if sg is not None else 0, y.ptr, *self._bw_one_launch_args(op, sv, dY), sv.P, y.shape[3], act, self.stream,
+                   tag="bytes_norm_bwd_apply", flops=float(dY.nbytes + y.nbytes + dY.nbytes))
+        return dY, False
+
+    def _bw_norm_bn_small(self, op, sv, dA, act):
+        y, dY = sv.y, self._alloc(sv.y.shape, BF16)
+        self._emit(self.L.bn_small_bwd, dA.ptr, y.ptr, y.dt, *self._bw_one_launch_args(op, sv, dY), sv.P, y.shape[3], act, self.stream,
+                   tag="bytes_norm_bwd_apply", flops=float(dA.nbytes + y.nbytes + dY.nbytes))
+        return dY, False
+
+    def _bw_norm_small(self, op, sv, dA, act):
+        y, b, dY = sv.y, op.attrs["b"], self._alloc(sv.y.shape, sv.y.dt)
+        self._emit(self.L.norm_small_bwd, dA.ptr, y.ptr, *self._bw_one_launch_args(op, sv, dY),
+                   self.store.grad_ptr(b) if b is not None else None, sv.NS, sv.P, y.shape[3], sv.G, act, self.stream,
+                   tag="bytes_norm_bwd_apply", flops=float(dA.nbytes + y.nbytes + dY.nbytes))
+        return dY, True
+
+    def _bw_norm_generic(self, op, sv, dA, act):
+        """The shared reduce + fused apply (_norm_bwd), or ONE launch on the mid-size batch-norm layers (phx_bn_bwd_onepass)."""
+        S, Lb, nv, b = self.stream, self.L, op.attrs["norm_vars"], op.attrs["b"]
+        y, NS, P, Gn, cout = sv.y, sv.NS, sv.P, sv.G, sv.y.shape[3]
+        nrep = _NREP if P >= _NREP_MINP else 1   # replicated accumulators: see k_norm_bwd_reduce
+        if _DETERMINISTIC and P >= _NREP_MINP:
+            nrep = 64                             # one block per replica there: more replicas = more blocks
+        sums2 = self._alloc_zeroed(nrep * NS * cout * 2)
+        self._alloc((NS * Gn * 2,), F32)         # (read by nothing; it keeps the plan's allocation sequence as it has always been)
+        dY = self._alloc(y.shape, y.dt)
+        # group / instance norm keep the convolution bias: its gradient (the per-channel sum of dY) comes out of the apply
+        # launch in closed form instead of a pass over dY (phx_norm_bwd_apply_fused_bias)
+        fs = sv.fsums if b is not None else None
+        bias = (fs.ptr if fs is not None else None, sv.fpivot.ptr if (fs is not None and sv.fpivot is not None) else None,
+                self.store.grad_ptr(b) if fs is not None else None)
+        if (sv.upconv is None and fs is None and sv.norm == "batch" and NS == 1 and Gn == cout and isinstance(dA, Buf)
+                and dA.dt == BF16 and y.dt == BF16 and _onepass_enabled() and Lb.bn_bwd_onepass_supported(P, cout, act)):
+            # mid-size batch-norm layers: ONE launch, (dA, y) read once and held in registers across a grid barrier
+            bar = self._alloc_zeroed(int(Lb.bn_bwd_onepass_barrier_words()))
+            self._barriers.append(bar)
+            self._emit(Lb.bn_bwd_onepass, dA.ptr, y.ptr, sv.scale.ptr, sv.shift.ptr, sv.mean.ptr, sv.rstd.ptr, self.store.ptr(nv["gamma"]),
+                       sums2.ptr, bar.ptr, dY.ptr, self.store.grad_ptr(nv["gamma"]), self.store.grad_ptr(nv["beta"]), P, cout, act, nrep, S,
+                       tag="bytes_norm_bwd_onepass", flops=float(dA.nbytes + y.nbytes + dY.nbytes))
         else:
-            dY = dA
-        dw = self.store.grad_ptr(W)
-        db = self.store.grad_ptr(b) if (b is not None and not db_done) else None
-        if upc is not None:
-            src = x.src                                  # the low-resolution tensor bilinear_upsample2D read
-            h, w = H // 2, Wd // 2
-            if db is not None:                           # (not reached with the closed-form bias gradient of the norm backward; kept exact)
-                self._emit(Lb.channel_sum_accumulate, dY.ptr, dY.dt, db, B * H * Wd, cout, S)
-            upconv.backward_prepare(self._emit, self._alloc, Lb, S, upc, dY, B, h, w, cout)
-            # (filter gradients before or after the data gradients: same step time, measured three alternating pairs)
-            upconv.backward_filters(self._emit, self._alloc, self._alloc_zeroed, Lb, S, upc, src, dY, dw, B, h, w, cin, cout)
-            xin = op.inputs[0].op.inputs[0]              # the gradient goes straight to the resize's input (its adjoint is part of the form)
-            if self.req.get(xin, False):
-                _, wd_w = self._packed(W)
-                self._add_grad(xin, write_fn=lambda g: upconv.backward_data(self._emit, self._alloc, Lb, S, upc, dY, wd_w, g, B, h, w, cin, cout))
-            return
-        if sv.get("general") is not None:
-            geo = sv["geo"]
-            self._emit(Lb.gconv2d_wgrad, x.ptr, x.dt, dY.ptr, dY.dt, dw, *geo, S)
-            if db is not None:
-                self._emit(Lb.channel_sum_accumulate, dY.ptr, dY.dt, db, dY.n // cout, cout, S)
-            xin = op.inputs[0]
-            if self.req.get(xin, False):
-                self._add_grad(xin, write_fn=lambda g: self._emit(Lb.gconv2d_dgrad, dY.ptr, dY.dt, self.store.ptr(W), g.ptr, g.dt,
-                                                                   *geo, S))
-            return
-        if sv.get("transposed") is not None:
-            kh, kw, sh, sw = sv["transposed"]
-            geo = (B, H, Wd, cin, cout, kh, kw, sh, sw)
-            self._emit(Lb.tconv2d_wgrad, x.ptr, x.dt, dY.ptr, dY.dt, dw, *geo, S)
-            if db is not None:
-                self._emit(Lb.channel_sum_accumulate, dY.ptr, dY.dt, db, dY.n // cout, cout, S)
-            xin = op.inputs[0]
-            if self.req.get(xin, False):
-                self._add_grad(xin, write_fn=lambda g: self._emit(Lb.tconv2d_dgrad, dY.ptr, dY.dt, self.store.ptr(W), g.ptr, g.dt,
-                                                                   *geo, S))
-            return
+            s2d = (sv.x.shape[1] // 2, sv.x.shape[2] // 2) if sv.upconv is not None else ()
+            self._norm_bwd(sv, nv, dA, dY, cout, act, nrep, sums2, bias=bias, tagged=True, s2d=s2d)
+        return dY, fs is not None
+
+    # ---- the units off the common path: stages 2 and 3 in one method each ------------------------------------------------------
+    def _bw_unit_upconv(self, op, sv, dY, db):
+        """Phase form (upconv.py): the gradient goes straight to the resize's input (its adjoint is part of the form)."""
+        S, Lb, W, upc = self.stream, self.L, op.attrs["W"], sv.upconv
+        B, H, Wd, cin, cout = self._unit_dims(op, sv)
+        h, w = H // 2, Wd // 2
+        if db is not None:                           # (not reached with the closed-form bias gradient of the norm backward; kept exact)
+            self._emit(Lb.channel_sum_accumulate, dY.ptr, dY.dt, db, B * H * Wd, cout, S)
+        upconv.backward_prepare(self._emit, self._alloc, Lb, S, upc, dY, B, h, w, cout)
+        # (filter gradients before or after the data gradients: same step time, measured three alternating pairs)
+        upconv.backward_filters(self._emit, self._alloc, self._alloc_zeroed, Lb, S, upc, sv.x.src, dY, self.store.grad_ptr(W), B, h, w, cin, cout)
+        xin = op.inputs[0].op.inputs[0]              # the low-resolution tensor bilinear_upsample2D read
+        if self.req.get(xin, False):
+            _, wd_w = self._packed(W)
+            self._add_grad(xin, write_fn=lambda g: upconv.backward_data(self._emit, self._alloc, Lb, S, upc, dY, wd_w, g, B, h, w, cin, cout))
+
+    def _bw_unit_direct(self, op, sv, dY, db, wgrad, dgrad):
+        """Filter, bias and data gradient of a unit on the direct kernels (gconv.hip / tconv.hip) with the geometry saved forward."""
+        S, x, W, cout = self.stream, sv.x, op.attrs["W"], self._unit_dims(op, sv)[4]
+        self._emit(wgrad, x.ptr, x.dt, dY.ptr, dY.dt, self.store.grad_ptr(W), *sv.geo, S)
+        if db is not None:
+            self._emit(self.L.channel_sum_accumulate, dY.ptr, dY.dt, db, dY.n // cout, cout, S)
+        if self.req.get(op.inputs[0], False):
+            self._add_grad(op.inputs[0], write_fn=lambda g: self._emit(dgrad, dY.ptr, dY.dt, self.store.ptr(W), g.ptr, g.dt, *sv.geo, S))
+
+    def _bw_unit_general(self, op, sv, dY, db):
+        self._bw_unit_direct(op, sv, dY, db, self.L.gconv2d_wgrad, self.L.gconv2d_dgrad)
+
+    def _bw_unit_transposed(self, op, sv, dY, db):
+        self._bw_unit_direct(op, sv, dY, db, self.L.tconv2d_wgrad, self.L.tconv2d_dgrad)
+
+    # ---- stage 2: the filter (and bias) gradient --------------------------------------------------------------------------------
+    def _bw_unit_filter(self, op, sv, dY, db):
         # (The filter gradient is a leaf of the backward graph; moving these launches to another lane, beside the data-
         # gradient chain, was measured 20 % SLOWER: both are bound by the same global->LDS path, so the kernel on the
         # critical path just gets half of it.)
-        if sv.get("head1x1") and cin % 8 == 0 and db is not None:
+        S, Lb, x, W, k = self.stream, self.L, sv.x, op.attrs["W"], op.attrs["ksize"]
+        B, H, Wd, cin, cout = self._unit_dims(op, sv)
+        dw = self.store.grad_ptr(W)
+        if sv.head1x1 and cin % 8 == 0 and db is not None:
             # a leaf of the backward graph: all heads share one launch after the lanes have joined (phx_head1x1_wgrad_multi)
             plan4 = (ctypes.c_int * 4)()
             Lb.head1x1_wgrad_plan(B * H * Wd, cin, cout, plan4)
             prod = self._norm_head.get(op)
-            au = self.saved[prod].get("a_unwritten") if prod is not None else None
-            if au is not None:      # the producer never wrote a = act(bn(y)): the job re-forms it from y (phx_head1x1_wgrad_multi, xscale)
-                self._headw_jobs.setdefault((au["y"].dt, cout), []).append((au["y"].ptr, dY.ptr, dw, db, B * H * Wd, cin, plan4[0], plan4[1],
-                                                                            plan4[2], plan4[3], (au["scale"].ptr, au["shift"].ptr, au["act"])))
-            else:
-                self._headw_jobs.setdefault((x.dt, cout), []).append((x.ptr, dY.ptr, dw, db, B * H * Wd, cin, plan4[0], plan4[1],
-                                                                       plan4[2], plan4[3]))
-        elif sv.get("head1x1"):
+            au = self.saved[prod].a_unwritten if prod is not None else None
+            src, extra = (x, ()) if au is None else (au["y"], ((au["scale"].ptr, au["shift"].ptr, au["act"]),))
+            # (au: the producer never wrote a = act(bn(y)) -- the job re-forms it from y: phx_head1x1_wgrad_multi, xscale)
+            self._headw_jobs.setdefault((src.dt, cout), []).append((src.ptr, dY.ptr, dw, db, B * H * Wd, cin, *plan4) + extra)
+        elif sv.head1x1:
             self._emit(Lb.head1x1_wgrad, x.ptr, x.dt, dY.ptr, dw, db, B * H * Wd, cin, cout, S)
-        elif sv.get("padded") or sv["mfma"]:
-            # padded layers (zero-padded input channels / 1x1 as centre tap): the gradient goes to a padded filter buffer
-            # first and a small kernel folds it into dw afterwards
-            padded = bool(sv.get("padded"))
-            ce = sv["cin_eff"] if padded else cin
-            tgt = self._alloc_zeroed(9 * ce * cout).ptr if padded else dw
-            dual = x if isinstance(x, DualBuf) else None       # concat-free input: the filter gradient reads the two tensors in place
-            xf = x if isinstance(x, XfBuf) else None           # unmaterialised input activation: re-formed from y by the kernel's loader
-            k1d = dual.k1 if dual is not None else 0
-            wsb = int(Lb.conv3x3_wgrad_ws_bytes_dual(B, H, Wd, ce, cout, k1d))
-            wsp = self._alloc((wsb // 4,), F32)      # per-layer workspace of partial filters (no cross-lane sharing)
-            plan6 = (ctypes.c_int * 6)()
-            Lb.conv3x3_wgrad_reduce_plan_dual(B, H, Wd, ce, cout, k1d, plan6)
-            rjob = (wsp.ptr, tgt, plan6[1], ce, cout, plan6[2], plan6[3], plan6[4], plan6[5])
-            if xf is None:
-                wargs = (x.ptr, dY.ptr, tgt, wsp.ptr, wsb, B, H, Wd, ce, cout)
-                dargs = (x.ptr, dual.b.ptr if dual is not None else None, k1d) + wargs[1:]      # (x, x2, K1, dy, ...)
-            wflops = 18.0 * cin * cout * B * H * Wd
-            deferred = False
-            # The filter gradients are leaves of the backward graph.  Small and mid-size maps: the launch itself is
-            # deferred -- one launch per kernel variant runs all such layers side by side after the lanes have joined
-            # (phx_conv3x3_wgrad_multi); their latency leaves the posterior / prior / likelihood chains.
-            nb = int(Lb.conv3x3_wgrad_multi_job_bytes())
-            jb, info = ctypes.create_string_buffer(nb), (ctypes.c_int * 9)()
-            if xf is None:       # (an unmaterialised input only exists on maps too large for the deferred launches: _xf_edge_ok)
-                Lb.conv3x3_wgrad_multi_job_dual(*dargs, _WGRAD_DEFER_BLOCKS, 0, jb, info)
-            if info[0]:
-                grp = self._wgm_jobs.setdefault(int(info[0]), dict(recs=[], blocks=0, lds=0))
-                Lb.conv3x3_wgrad_multi_job_dual(*dargs, _WGRAD_DEFER_BLOCKS, grp["blocks"], jb, info)
-                grp["recs"].append(jb.raw)
-                grp["blocks"] += int(info[1])
-                grp["lds"] = max(grp["lds"], int(info[2]))
-                if info[3]:
-                    self._wgr_jobs.append((wsp.ptr, tgt, info[4], ce, cout, info[5], info[6], info[7], info[8]))
-                deferred = True
-            if deferred:
-                pass
-            elif plan6[0]:
-                # large maps: the launch stays here, only the sum over its partial filters is deferred to ONE launch for all
-                # layers (phx_wgrad_reduce_multi)
-                if xf is not None:
-                    self._emit(Lb.conv3x3_wgrad_mfma_bf16_partial_xf, xf.y.ptr, xf.scale.ptr, xf.shift.ptr, dY.ptr, tgt, wsp.ptr, wsb,
-                               B, H, Wd, ce, cout, S, tag="conv3x3_mfma_wgrad", flops=wflops)
-                elif dual is not None:
-                    self._emit(Lb.conv3x3_wgrad_mfma_bf16_dual, *dargs, 0, S, tag="conv3x3_mfma_wgrad", flops=wflops)
-                else:
-                    self._emit(Lb.conv3x3_wgrad_mfma_bf16_partial, *wargs, S, tag="conv3x3_mfma_wgrad", flops=wflops)
-                self._wgr_jobs.append(rjob)
-                deferred = True
-            elif xf is not None:
-                raise rt.PhxError("filter gradient of an unmaterialised input activation without a workspace plan (see _xf_edge_ok)")
-            elif dual is not None:
-                self._emit(Lb.conv3x3_wgrad_mfma_bf16_dual, *dargs, 1, S, tag="conv3x3_mfma_wgrad", flops=wflops)
-            else:
-                self._emit(Lb.conv3x3_wgrad_mfma_bf16, *wargs, S, tag="conv3x3_mfma_wgrad", flops=wflops)
-            if padded:
-                unpad = (Lb.unpad_filter_grad_center if sv.get("k1") else Lb.unpad_filter_grad_accumulate, (tgt, dw, cin, ce, cout))
-                if deferred:
-                    self._tail_jobs.append(unpad)             # after the deferred launches, on lane 0
-                else:
-                    self._emit(unpad[0], *unpad[1], S)
-            if db is not None:
-                self._emit(Lb.channel_sum_accumulate, dY.ptr, dY.dt, db, B * H * Wd, cout, S)
-        elif (sv.get("f32m") and k == 3 and x.dt == F32 and dY.dt == F32 and isinstance(x, Buf)
+        elif sv.padded or sv.mfma:
+            self._bw_filter_mfma(op, sv, dY, dw, db)
+        elif (sv.f32m and k == 3 and x.dt == F32 and dY.dt == F32 and isinstance(x, Buf)
               and Lb.conv3x3_f32_mfma_wgrad_supported(B, H, Wd, cin, cout)):
             # fp32 plans: the filter gradient on the fp32 matrix instruction; partial filters in a workspace, summed in slice order
             # (a fixed order in every mode)
@@ -513,18 +441,101 @@ class BackwardLowering:
             ws = self._alloc((wsb // 4,), F32)
             self._emit(Lb.conv3x3_f32_mfma_wgrad, x.ptr, dY.ptr, dw, db, ws.ptr, wsb, B, H, Wd, cin, cout, S,
                        tag="conv3x3_f32_mfma_wgrad", flops=18.0 * cin * cout * B * H * Wd)
+        elif _DETERMINISTIC:
+            # ordered partial filters: the fixed summation order at full parallelism (the plain entry point's deterministic
+            # launch is one block per channel block -- 0.47 s instead of 0.1 s per fp32 training step at n0 = 32, batch 12)
+            wsb = int(Lb.conv2d_direct_wgrad_ordered_ws_bytes(B, H, Wd, cin, cout, k))
+            ws = self._alloc((wsb // 4,), F32) if wsb else None
+            self._emit(Lb.conv2d_direct_wgrad_ordered, x.ptr, x.dt, dY.ptr, dY.dt, dw, db, ws.ptr if ws is not None else None, wsb,
+                       B, H, Wd, cin, cout, k, S)
         else:
-            if _DETERMINISTIC:
-                # ordered partial filters: the fixed summation order at full parallelism (the plain entry point's deterministic
-                # launch is one block per channel block -- 0.47 s instead of 0.1 s per fp32 training step at n0 = 32, batch 12)
-                wsb = int(Lb.conv2d_direct_wgrad_ordered_ws_bytes(B, H, Wd, cin, cout, k))
-                ws = self._alloc((wsb // 4,), F32) if wsb else None
-                self._emit(Lb.conv2d_direct_wgrad_ordered, x.ptr, x.dt, dY.ptr, dY.dt, dw, db, ws.ptr if ws is not None else None, wsb,
-                           B, H, Wd, cin, cout, k, S)
+            self._emit(Lb.conv2d_direct_wgrad, x.ptr, x.dt, dY.ptr, dY.dt, dw, db, B, H, Wd, cin, cout, k, S)
+
+    def _bw_filter_mfma(self, op, sv, dY, dw, db):
+        """bf16 MFMA filter gradient.  Padded layers (zero-padded input channels / 1x1 as centre tap): the gradient goes to a padded
+        filter buffer first and a small kernel folds it into dw afterwards."""
+        S, Lb, x = self.stream, self.L, sv.x
+        B, H, Wd, cin, cout = self._unit_dims(op, sv)
+        ce = sv.cin_eff if sv.padded else cin
+        tgt = self._alloc_zeroed(9 * ce * cout).ptr if sv.padded else dw
+        dual = x if isinstance(x, DualBuf) else None       # concat-free input: the filter gradient reads the two tensors in place
+        xf = x if isinstance(x, XfBuf) else None           # unmaterialised input activation: re-formed from y by the kernel's loader
+        k1d = dual.k1 if dual is not None else 0
+        wsb = int(Lb.conv3x3_wgrad_ws_bytes_dual(B, H, Wd, ce, cout, k1d))
+        wsp = self._alloc((wsb // 4,), F32)      # per-layer workspace of partial filters (no cross-lane sharing)
+        plan6 = (ctypes.c_int * 6)()
+        Lb.conv3x3_wgrad_reduce_plan_dual(B, H, Wd, ce, cout, k1d, plan6)
+        if xf is None:
+            wargs = (x.ptr, dY.ptr, tgt, wsp.ptr, wsb, B, H, Wd, ce, cout)
+            dargs = (x.ptr, dual.b.ptr if dual is not None else None, k1d) + wargs[1:]      # (x, x2, K1, dy, ...)
+        tag = dict(tag="conv3x3_mfma_wgrad", flops=18.0 * cin * cout * B * H * Wd)
+        # The filter gradients are leaves of the backward graph.  Small and mid-size maps: the launch itself is
+        # deferred -- one launch per kernel variant runs all such layers side by side after the lanes have joined
+        # (phx_conv3x3_wgrad_multi); their latency leaves the posterior / prior / likelihood chains.
+        # (an unmaterialised input only exists on maps too large for the deferred launches: _xf_edge_ok)
+        deferred = xf is None and self._defer_filter_gradient(dargs, wsp, tgt, ce, cout)
+        if deferred:
+            pass
+        elif plan6[0]:
+            # large maps: the launch stays here, only the sum over its partial filters is deferred to ONE launch for all
+            # layers (phx_wgrad_reduce_multi)
+            if xf is not None:
+                self._emit(Lb.conv3x3_wgrad_mfma_bf16_partial_xf, xf.y.ptr, xf.scale.ptr, xf.shift.ptr, dY.ptr, tgt, wsp.ptr, wsb,
+                           B, H, Wd, ce, cout, S, **tag)
+            elif dual is not None:
+                self._emit(Lb.conv3x3_wgrad_mfma_bf16_dual, *dargs, 0, S, **tag)
             else:
-                self._emit(Lb.conv2d_direct_wgrad, x.ptr, x.dt, dY.ptr, dY.dt, dw, db, B, H, Wd, cin, cout, k, S)
+                self._emit(Lb.conv3x3_wgrad_mfma_bf16_partial, *wargs, S, **tag)
+            self._wgr_jobs.append((wsp.ptr, tgt, plan6[1], ce, cout, plan6[2], plan6[3], plan6[4], plan6[5]))
+            deferred = True
+        elif xf is not None:
+            raise rt.PhxError("filter gradient of an unmaterialised input activation without a workspace plan (see _xf_edge_ok)")
+        elif dual is not None:
+            self._emit(Lb.conv3x3_wgrad_mfma_bf16_dual, *dargs, 1, S, **tag)
+        else:
+            self._emit(Lb.conv3x3_wgrad_mfma_bf16, *wargs, S, **tag)
+        if sv.padded:
+            unpad = (Lb.unpad_filter_grad_center if sv.k1 else Lb.unpad_filter_grad_accumulate, (tgt, dw, cin, ce, cout))
+            if deferred:
+                self._tail_jobs.append(unpad)             # after the deferred launches, on lane 0
+            else:
+                self._emit(unpad[0], *unpad[1], S)
+        if db is not None:
+            self._emit(Lb.channel_sum_accumulate, dY.ptr, dY.dt, db, B * H * Wd, cout, S)
+
+    def _defer_filter_gradient(self, dargs, wsp, tgt, ce, cout):
+        """Queue the layer's job record for its kernel variant's deferred launch, if the library defers this shape -> deferred?"""
+        Lb = self.L
+        jb, info = ctypes.create_string_buffer(int(Lb.conv3x3_wgrad_multi_job_bytes())), (ctypes.c_int * 9)()
+        Lb.conv3x3_wgrad_multi_job_dual(*dargs, _WGRAD_DEFER_BLOCKS, 0, jb, info)
+        if not info[0]:
+            return False
+        grp = self._wgm_jobs.setdefault(int(info[0]), dict(recs=[], blocks=0, lds=0))
+        Lb.conv3x3_wgrad_multi_job_dual(*dargs, _WGRAD_DEFER_BLOCKS, grp["blocks"], jb, info)
+        grp["recs"].append(jb.raw)
+        grp["blocks"] += int(info[1])
+        grp["lds"] = max(grp["lds"], int(info[2]))
+        if info[3]:
+            self._wgr_jobs.append((wsp.ptr, tgt, info[4], ce, cout, info[5], info[6], info[7], info[8]))
+        return True
+
+    # ---- stage 3: the data gradient ---------------------------------------------------------------------------------------------
+    def _bw_unit_data(self, op, sv, dY):
+        S, Lb, x, W, k = self.stream, self.L, sv.x, op.attrs["W"], op.attrs["ksize"]
+        B, H, Wd, cin, cout = self._unit_dims(op, sv)
         xin = op.inputs[0]
-        if isinstance(x, DualBuf) and self.req.get(xin, False):
+        if not self.req.get(xin, False):
+            return
+        dtag = dict(tag="conv3x3_mfma_dgrad", flops=18.0 * cin * cout * B * H * Wd)
+
+        def mfma_dgrad(g):
+            """The 3x3 data gradient on the MFMA path into g (None: the split-K slices stay in the workspace) -> the workspace"""
+            wsb = int(Lb.conv3x3_mfma_ws_bytes(B, H, Wd, cout, cin))
+            ws = self._alloc((wsb // 4,), F32) if wsb else None      # split-K slices (small maps)
+            self._emit(Lb.conv3x3_mfma_bf16_ws, dY.ptr, wd.ptr, g.ptr if g is not None else None, None, 0, None, ws.ptr if ws else None, wsb,
+                       B, H, Wd, cout, cin, S, **dtag)
+            return ws
+        if isinstance(x, DualBuf):
             # concat-free: the two halves of d(concat) are written straight to the gradients of the concatenated tensors
             ta, tb = xin.op.inputs
             _, wd = self._packed(W)
@@ -532,58 +543,43 @@ class BackwardLowering:
             wsb = int(Lb.conv3x3_mfma_ws_bytes(B, H, Wd, cout, cin))
             ws = self._alloc((wsb // 4,), F32) if wsb else None      # split-K slices (small maps)
             self._emit(Lb.conv3x3_mfma_bf16_dual, dY.ptr, None, 0, wd.ptr, g1.ptr, g2.ptr, x.k1, None, None, 0, None, 0,
-                       ws.ptr if ws else None, wsb, B, H, Wd, cout, cin, S,
-                       tag="conv3x3_mfma_dgrad", flops=18.0 * cin * cout * B * H * Wd)
+                       ws.ptr if ws else None, wsb, B, H, Wd, cout, cin, S, **dtag)
             for t, gb in ((ta, g1), (tb, g2)):
                 if self.req.get(t, False):
                     self._add_grad(t, buf=gb)
-        elif self.req.get(xin, False):
-            if sv.get("norm_head"):              # no data-gradient launch: the producer's norm backward forms dA = dY W^T itself
-                self._add_grad(xin, buf=HeadGrad(self.val[xin], dY, self.store.ptr(W), cout))
-            elif sv.get("head1x1"):
-                self._add_grad(xin, write_fn=lambda g: self._emit(
-                    Lb.head1x1_dgrad, dY.ptr, self.store.ptr(W), g.ptr, g.dt, B * H * Wd, cin, cout, S))
-            elif sv.get("padded"):
-                ce, wdp = sv["cin_eff"], sv["wd_pad"]
+        elif sv.norm_head:              # no data-gradient launch: the producer's norm backward forms dA = dY W^T itself
+            self._add_grad(xin, buf=HeadGrad(self.val[xin], dY, self.store.ptr(W), cout))
+        elif sv.head1x1:
+            self._add_grad(xin, write_fn=lambda g: self._emit(
+                Lb.head1x1_dgrad, dY.ptr, self.store.ptr(W), g.ptr, g.dt, B * H * Wd, cin, cout, S))
+        elif sv.padded:
+            ce, wdp = sv.cin_eff, sv.wd_pad
 
-                def wr(g):
-                    gp = self._alloc((B, H, Wd, ce), BF16)
-                    self._emit(Lb.conv3x3_mfma_bf16, dY.ptr, wdp.ptr, gp.ptr, None, 0, None, B, H, Wd, cout, ce, S,
-                               tag="conv3x3_mfma_dgrad", flops=18.0 * cin * cout * B * H * Wd)
+            def wr(g):
+                inplace = ce == cin and g.dt == BF16        # nothing to strip / cast: the data gradient is written in place
+                gp = g if inplace else self._alloc((B, H, Wd, ce), BF16)
+                self._emit(Lb.conv3x3_mfma_bf16, dY.ptr, wdp.ptr, gp.ptr, None, 0, None, B, H, Wd, cout, ce, S, **dtag)
+                if not inplace:
                     self._emit(Lb.unpad_channels_bf16, gp.ptr, g.ptr, g.dt, cin, ce, B * H * Wd, S)
-                if ce == cin and self.val[xin].dt == BF16:      # nothing to strip / cast: the data gradient is written in place
-                    self._add_grad(xin, write_fn=lambda g: self._emit(
-                        Lb.conv3x3_mfma_bf16, dY.ptr, wdp.ptr, g.ptr, None, 0, None, B, H, Wd, cout, ce, S,
-                        tag="conv3x3_mfma_dgrad", flops=18.0 * cin * cout * B * H * Wd))
-                else:
-                    self._add_grad(xin, write_fn=wr)
-            elif sv["mfma"] and self._slice_grad_ok(op, xin, B, H, Wd, cout, cin):
-                # 2 x 2 / 4 x 4 levels: the split-K data gradient leaves its fp32 slices for the producer's one-launch batch-norm
-                # backward (phx_bn_wide_bwd sums them): no finishing launch, no bf16 gradient tensor
-                _, wd = self._packed(W)
-                wsb = int(Lb.conv3x3_mfma_ws_bytes(B, H, Wd, cout, cin))
-                ws = self._alloc((wsb // 4,), F32)
-                self._emit(Lb.conv3x3_mfma_bf16_ws, dY.ptr, wd.ptr, None, None, 0, None, ws.ptr, wsb,
-                           B, H, Wd, cout, cin, S, tag="conv3x3_mfma_dgrad", flops=18.0 * cin * cout * B * H * Wd)
-                self._add_grad(xin, buf=SliceGrad(self.val[xin], ws, int(Lb.conv3x3_mfma_ksplit(B, H, Wd, cout, cin))))
-            elif sv["mfma"]:
-                _, wd = self._packed(W)
+            self._add_grad(xin, write_fn=wr)
+        elif sv.mfma and self._slice_grad_ok(op, xin, B, H, Wd, cout, cin):
+            # 2 x 2 / 4 x 4 levels: the split-K data gradient leaves its fp32 slices for the producer's one-launch batch-norm
+            # backward (phx_bn_wide_bwd sums them): no finishing launch, no bf16 gradient tensor
+            _, wd = self._packed(W)
+            ws = mfma_dgrad(None)
+            self._add_grad(xin, buf=SliceGrad(self.val[xin], ws, int(Lb.conv3x3_mfma_ksplit(B, H, Wd, cout, cin))))
+        elif sv.mfma:
+            _, wd = self._packed(W)
+            self._add_grad(xin, write_fn=mfma_dgrad)
+        elif sv.f32m and cin % 32 == 0 and dY.dt == F32 and self._wpk32.get(W.name, (None, None))[1] is not None:
+            wd32 = self._wpk32[W.name][1]
 
-                def wr_mfma(g):
-                    wsb = int(Lb.conv3x3_mfma_ws_bytes(B, H, Wd, cout, cin))
-                    ws = self._alloc((wsb // 4,), F32) if wsb else None      # split-K slices (small maps)
-                    self._emit(Lb.conv3x3_mfma_bf16_ws, dY.ptr, wd.ptr, g.ptr, None, 0, None, ws.ptr if ws else None, wsb,
-                               B, H, Wd, cout, cin, S, tag="conv3x3_mfma_dgrad", flops=18.0 * cin * cout * B * H * Wd)
-                self._add_grad(xin, write_fn=wr_mfma)
-            elif sv.get("f32m") and cin % 32 == 0 and dY.dt == F32 and self._wpk32.get(W.name, (None, None))[1] is not None:
-                wd32 = self._wpk32[W.name][1]
-
-                def wr_f32m(g):
-                    assert g.dt == F32
-                    self._emit(Lb.conv3x3_f32_mfma, dY.ptr, wd32.ptr, None, g.ptr, B, H, Wd, cout, cin, 0, S,
-                               tag="conv3x3_f32_mfma_dgrad", flops=18.0 * cin * cout * B * H * Wd)
-                self._add_grad(xin, write_fn=wr_f32m)
-            else:
-                self._add_grad(xin, write_fn=lambda g: self._emit(
-                    Lb.conv2d_direct, dY.ptr, dY.dt, self.store.ptr(W), None, g.ptr, g.dt, B, H, Wd, cin, cout, k, 0,
-                    1, None, S))
+            def wr_f32m(g):
+                assert g.dt == F32
+                self._emit(Lb.conv3x3_f32_mfma, dY.ptr, wd32.ptr, None, g.ptr, B, H, Wd, cout, cin, 0, S,
+                           tag="conv3x3_f32_mfma_dgrad", flops=18.0 * cin * cout * B * H * Wd)
+            self._add_grad(xin, write_fn=wr_f32m)
+        else:
+            self._add_grad(xin, write_fn=lambda g: self._emit(
+                Lb.conv2d_direct, dY.ptr, dY.dt, self.store.ptr(W), None, g.ptr, g.dt, B, H, Wd, cin, cout, k, 0,
+                1, None, S))

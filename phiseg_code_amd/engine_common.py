@@ -1,6 +1,7 @@
 """Shared by the engine modules (engine.py: parameter store, plan construction, capture and replay; engine_forward.py: lowering of
 the forward operators; engine_backward.py: the reverse-mode backward pass): dtype codes, schedule constants, device buffers."""
 import ctypes
+import enum
 import os
 
 import numpy as np
@@ -10,7 +11,7 @@ from phiseg_code_amd import graph as G
 from phiseg_code_amd import runtime as rt
 from phiseg_code_amd.tfwrapper import normalisation as tfnorm
 
-__all__ = ['F32', 'BF16', 'U8', '_TORCH_DT', '_NP_DT', '_ESIZE', '_LIK_SIDE_MAXLVL', '_WGRAD_DEFER_BLOCKS', '_NREP', '_NREP_MINP', '_STAMPS', '_DETERMINISTIC', '_BN_SMALL', '_BN_SMALL_F32', '_BN_WIDE', '_BN_WIDE_MAXLINES', '_SKIP_HEAD_A', '_POOL_FUSE', '_xf_enabled', '_upconv_min_h', 'UpBuf', '_fgn_mode', '_dual_enabled', '_f32_mfma_enabled', '_onepass_enabled', '_noop', '_device', 'live_variables', 'device_sync', 'Buf', 'DualBuf', 'HeadGrad', 'SliceGrad', 'XfBuf']
+__all__ = ['F32', 'BF16', 'U8', '_TORCH_DT', '_NP_DT', '_ESIZE', '_LIK_SIDE_MAXLVL', '_WGRAD_DEFER_BLOCKS', '_NREP', '_NREP_MINP', '_STAMPS', '_DETERMINISTIC', '_BN_SMALL', '_BN_SMALL_F32', '_BN_WIDE', '_BN_WIDE_MAXLINES', '_SKIP_HEAD_A', '_POOL_FUSE', '_xf_enabled', '_upconv_min_h', 'UpBuf', '_fgn_mode', '_dual_enabled', '_f32_mfma_enabled', '_onepass_enabled', '_noop', '_device', 'live_variables', 'device_sync', 'Buf', 'DualBuf', 'HeadGrad', 'SliceGrad', 'XfBuf', 'NormRoute', 'StatsSource', 'ConvSaved']
 
 F32, BF16, U8 = rt.F32, rt.BF16, 2
 _TORCH_DT = {F32: torch.float32, BF16: torch.bfloat16, U8: torch.uint8}
@@ -186,3 +187,34 @@ class UpBuf:
     @property
     def nbytes(self):
         return self.n * _ESIZE[self.dt]
+
+
+class NormRoute(enum.Enum):
+    """How a conv unit's normalisation is lowered (engine_forward.conv_norm_route chooses; DESIGN.md section 1 has the table)."""
+    NONE, INFER_FOLDED, INFER, BN_WIDE, BN_SMALL_F32Y, BN_SMALL, FGN, NORM_SMALL, GENERIC = range(9)
+
+
+class StatsSource(enum.Enum):
+    """Where the GENERIC route's per-channel sums come from."""
+    PARTIALS, PARTIALS_NS, ATOMIC, DIRECT, PIVOT_PASS = range(5)
+
+
+class ConvSaved:
+    """What the forward lowering of a conv_unit / transposed / general unit / norm_act leaves for the backward pass (Plan.saved[op]).
+    An unknown attribute raises on read and on write."""
+    _OPTIONAL = dict(route=NormRoute.NONE, y=None, scale=None, shift=None, mean=None, rstd=None, NS=None, P=None, G=None, wd_pad=None,
+                     upconv=None, a_unwritten=None, fsums=None, fpivot=None, transposed=None, general=None, geo=None, f32m=False,
+                     norm_head=False, latent=False)
+    __slots__ = ("x", "out", "norm", "mfma", "padded", "cin_eff", "k1", "head1x1") + tuple(_OPTIONAL)
+
+    def __init__(self, x, out, norm, mfma, padded, cin_eff, k1, head1x1, **optional):
+        self.x, self.out, self.norm, self.mfma, self.padded, self.cin_eff, self.k1, self.head1x1 = x, out, norm, mfma, padded, cin_eff, k1, head1x1
+        for key, default in self._OPTIONAL.items():
+            setattr(self, key, optional.pop(key, default))
+        if optional:
+            raise TypeError("ConvSaved: unknown fields %s" % sorted(optional))
+
+    @classmethod
+    def plain(cls, x, out, norm, cin_eff, head1x1=False, **optional):
+        """A unit off the matrix-core paths: nothing packed, nothing padded."""
+        return cls(x, out, norm, False, False, cin_eff, False, head1x1, **optional)

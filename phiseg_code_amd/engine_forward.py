@@ -2,7 +2,7 @@
 of that operator into the plan's launch list and records what the backward pass needs (`self.saved`).  Replaces the forward half of
 what TensorFlow builds for `sess.run` in the reference (phiseg/phiseg_model.py:20-157, tfwrapper/layers.py, model_zoo/*.py)."""
 import ctypes
-import os
+import types
 
 import numpy as np
 import torch
@@ -13,6 +13,49 @@ from phiseg_code_amd import upconv
 from phiseg_code_amd.tfwrapper import normalisation as tfnorm
 from phiseg_code_amd.engine_common import *  # noqa: F401,F403
 from phiseg_code_amd.engine_common import _BN_SMALL, _BN_SMALL_F32, _BN_WIDE, _BN_WIDE_MAXLINES, _SKIP_HEAD_A, _DETERMINISTIC, _NREP, _NREP_MINP, _fgn_mode, _dual_enabled, _noop, _device, _TORCH_DT, _NP_DT, _ESIZE, _LIK_SIDE_MAXLVL, _WGRAD_DEFER_BLOCKS, _STAMPS  # noqa: F401
+
+
+def conv_norm_route(Lb, norm, training, bw, act_dt, x_dt, y_dt, out_dt, B, H, Wd, cin_eff, cout, Gn, mfma, head1x1, concat_free, upsampled,
+                    deterministic=_DETERMINISTIC, fgn=None):
+    """Which lowering the normalisation of a plain conv unit takes -> (NormRoute, StatsSource or None).  Pure: the library handle
+    answers capability queries, everything else is a plain value (concat_free / upsampled: the input is a DualBuf / an UpBuf;
+    fgn: the PHX_FGN mode, read from the environment when None).  DESIGN.md section 1 lists the routes."""
+    fgn = _fgn_mode() if fgn is None else fgn
+    if norm is None:
+        return NormRoute.NONE, None
+    NS, P = (1, B * H * Wd) if norm == "batch" else (B, H * Wd)
+    if norm == "batch" and not training:
+        return (NormRoute.INFER_FOLDED if (mfma and not head1x1 and not bw) else NormRoute.INFER), None
+    both_bf16 = y_dt == BF16 and out_dt == BF16
+    if norm == "batch" and both_bf16 and P <= _BN_SMALL and Lb.bn_small_supported(P, cout, BF16):
+        if mfma and not head1x1 and _BN_SMALL_F32 and Lb.conv3x3_mfma_f32out_supported(B, H, Wd, cin_eff, cout):
+            nz = int(Lb.conv3x3_mfma_ksplit(B, H, Wd, cin_eff, cout))
+            wide = bool(_BN_WIDE and Lb.bn_wide_supported(P, cout) and P * nz <= _BN_WIDE_MAXLINES)
+            return (NormRoute.BN_WIDE if wide else NormRoute.BN_SMALL_F32Y), None
+        return NormRoute.BN_SMALL, None
+    if (norm != "batch" and mfma and not head1x1 and not concat_free and not deterministic and (fgn >= 2 or (fgn == 1 and Gn != cout))
+            and both_bf16 and x_dt == BF16 and Lb.conv3x3_fgn_supported(B, H, Wd, cin_eff, cout, Gn)
+            and Lb.norm_small_supported(NS, P, cout, Gn, BF16)):
+        return NormRoute.FGN, None
+    if norm != "batch" and both_bf16 and Lb.norm_small_supported(NS, P, cout, Gn, BF16):
+        return NormRoute.NORM_SMALL, None
+    small = P <= 16384 or act_dt == F32
+    tiles = Lb.conv3x3_mfma_bf16_tiles_dual if concat_free else Lb.conv3x3_mfma_bf16_tiles
+    if upsampled:
+        stats = StatsSource.PIVOT_PASS
+    elif norm == "batch" and mfma and not small:
+        stats = StatsSource.PARTIALS
+    elif (norm == "batch" and mfma and small and not deterministic and not head1x1 and act_dt == BF16
+          and Lb.conv3x3_mfma_stats_atomic_supported(B, H, Wd, cin_eff, cout)):
+        stats = StatsSource.ATOMIC
+    elif (norm != "batch" and mfma and not head1x1 and act_dt == BF16 and H % 16 == 0 and Wd % 16 == 0
+          and int(tiles(B, H, Wd, cin_eff, cout)) % B == 0):
+        stats = StatsSource.PARTIALS_NS
+    elif norm == "batch" and not small and not deterministic:
+        stats = StatsSource.DIRECT
+    else:
+        stats = StatsSource.PIVOT_PASS
+    return NormRoute.GENERIC, stats
 
 
 class ForwardLowering:
@@ -124,6 +167,52 @@ class ForwardLowering:
             self._pack32_jobs[rec[2]][2] = rec[1].ptr
         return rec[0], rec[1]
 
+    # ---- the generic normalisation lowering, shared by the conv units, the transposed / general units and norm_act --------------
+    def _norm_vectors(self, sv, B, HW, C, num_groups):
+        """Statistics geometry of sv.norm on a [B, HW, C] tensor -- NS statistics sets of P values per channel, G groups -- and the
+        four per-layer vectors, all recorded on `sv`."""
+        if sv.norm == "batch":
+            sv.NS, sv.P, sv.G = 1, B * HW, C
+        else:
+            sv.G = C if sv.norm == "instance" else (num_groups or max(2, C // 16))
+            sv.NS, sv.P = B, HW
+        sv.scale, sv.shift = self._alloc((sv.NS * C,), F32), self._alloc((sv.NS * C,), F32)
+        sv.mean, sv.rstd = self._alloc((sv.NS * sv.G,), F32), self._alloc((sv.NS * sv.G,), F32)
+
+    def _moving_args(self, nv, upd):
+        """(moving mean, moving variance, momentum) arguments: the moving statistics move only in a training plan's batch norm."""
+        if not upd:
+            return None, None, 0.0
+        return self.store.ptr(nv["moving_mean"]), self.store.ptr(nv["moving_variance"]), 1.0 - tfnorm.BN_DECAY
+
+    def _norm_apply_args(self, sv, a, y, sums, pivot, out, C, act, training):
+        """Arguments of phx_norm_apply_fused (and its _d2s / _head forms) up to the stream."""
+        nv = a["norm_vars"]
+        return (y.ptr, y.dt, sums.ptr, pivot.ptr if pivot is not None else None, self.store.ptr(nv["gamma"]), self.store.ptr(nv["beta"]),
+                tfnorm.EPS[sv.norm], out.ptr, out.dt, sv.mean.ptr, sv.rstd.ptr, sv.scale.ptr, sv.shift.ptr,
+                *self._moving_args(nv, sv.norm == "batch" and training and self.loss is not None), sv.NS, sv.P, C, sv.G, act)
+
+    def _norm_stats_pass(self, sv, y, sums, C, conv=_noop):
+        """Shifted (pivot) sums of y in a stand-alone pass, behind the launch `conv` that writes y (if any); -> the pivot vector."""
+        pivot = self._alloc((sv.NS * C,), F32)
+        conv()
+        self._emit(self.L.norm_stats, y.ptr, y.dt, sums.ptr, pivot.ptr, sv.NS, sv.P, C, self.stream)
+        return pivot
+
+    def _norm_fwd(self, sv, a, y, out, C, act, training, conv=_noop):
+        """out = act(norm(y)) the generic way: inference-mode batch norm as scale / shift + phx_affine_act, anything else as a
+        statistics pass + the fused apply.  `conv`: the launch that writes y, where the caller has not emitted it yet."""
+        S, Lb, nv = self.stream, self.L, a["norm_vars"]
+        if sv.norm == "batch" and not training:
+            self._emit(Lb.bn_infer_scale_shift, self.store.ptr(nv["gamma"]), self.store.ptr(nv["beta"]), self.store.ptr(nv["moving_mean"]),
+                       self.store.ptr(nv["moving_variance"]), tfnorm.EPS[sv.norm], C, sv.scale.ptr, sv.shift.ptr, S)
+            conv()
+            self._emit(Lb.affine_act, y.ptr, y.dt, sv.scale.ptr, sv.shift.ptr, out.ptr, out.dt, sv.NS, sv.P, C, act, S)
+            return
+        sums = self._alloc_zeroed(sv.NS * C * 2)
+        pivot = self._norm_stats_pass(sv, y, sums, C, conv)
+        self._emit(Lb.norm_apply_fused, *self._norm_apply_args(sv, a, y, sums, pivot, out, C, act, training), S)
+
     def _fw_tconv_unit(self, op, bw):
         """tf.nn.conv2d_transpose -> [bias] -> [norm] -> act (tfwrapper/layers.py:197-258) on the direct kernels of tconv.hip;
         the normalisation runs as statistics pass + fused apply on the up-sampled tensor."""
@@ -145,44 +234,19 @@ class ForwardLowering:
             conv_fwd = Lb.tconv2d_fwd
         out = self._alloc_like(op.outputs[0])
         self.val[op.outputs[0]] = out
-        Ho, Wo = out.shape[1], out.shape[2]
         act = rt.ACT_CODES[a["act"]]
         norm = a["norm"]
         training = a["training"] if isinstance(a["training"], bool) else self.training
         wptr, bptr = self.store.ptr(W), (self.store.ptr(b) if b is not None else None)
-        st = dict(x=x, out=out, mfma=False, norm=norm, padded=False, cin_eff=cin, k1=False, head1x1=False,
-                  transposed=a.get("transposed"), general=a.get("general"), geo=geo)
+        sv = self.saved[op] = ConvSaved.plain(x, out, norm, cin, transposed=a.get("transposed"), general=a.get("general"), geo=geo)
         if norm is None:
             self._emit(conv_fwd, x.ptr, x.dt, wptr, bptr, out.ptr, out.dt, *geo, act, S)
-            self.saved[op] = st
             return
-        nv = a["norm_vars"]
-        gptr, beptr = self.store.ptr(nv["gamma"]), self.store.ptr(nv["beta"])
-        y = self._alloc(out.shape, out.dt)
+        y = sv.y = self._alloc(out.shape, out.dt)
         self._emit(conv_fwd, x.ptr, x.dt, wptr, bptr, y.ptr, y.dt, *geo, 0, S)
-        if norm == "batch":
-            NS, P, Gn = 1, B * Ho * Wo, cout
-        else:
-            Gn = cout if norm == "instance" else (a["num_groups"] or max(2, cout // 16))
-            NS, P = B, Ho * Wo
-        scale, shift = self._alloc((NS * cout,), F32), self._alloc((NS * cout,), F32)
-        mean, rstd = self._alloc((NS * Gn,), F32), self._alloc((NS * Gn,), F32)
-        eps = tfnorm.EPS[norm]
-        if norm == "batch" and not training:
-            self._emit(Lb.bn_infer_scale_shift, gptr, beptr, self.store.ptr(nv["moving_mean"]),
-                       self.store.ptr(nv["moving_variance"]), eps, cout, scale.ptr, shift.ptr, S)
-            self._emit(Lb.affine_act, y.ptr, y.dt, scale.ptr, shift.ptr, out.ptr, out.dt, NS, P, cout, act, S)
-        else:
-            sums = self._alloc_zeroed(NS * cout * 2)
-            pivot = self._alloc((NS * cout,), F32)
-            self._emit(Lb.norm_stats, y.ptr, y.dt, sums.ptr, pivot.ptr, NS, P, cout, S)
-            upd = norm == "batch" and training and self.loss is not None
-            self._emit(Lb.norm_apply_fused, y.ptr, y.dt, sums.ptr, pivot.ptr, gptr, beptr, eps, out.ptr, out.dt, mean.ptr, rstd.ptr,
-                       scale.ptr, shift.ptr, self.store.ptr(nv["moving_mean"]) if upd else None,
-                       self.store.ptr(nv["moving_variance"]) if upd else None, (1.0 - tfnorm.BN_DECAY) if upd else 0.0,
-                       NS, P, cout, Gn, act, S)
-        st.update(y=y, scale=scale, shift=shift, mean=mean, rstd=rstd, NS=NS, P=P, G=Gn)
-        self.saved[op] = st
+        self._norm_vectors(sv, B, out.shape[1] * out.shape[2], cout, a["num_groups"])
+        sv.route = NormRoute.INFER if (norm == "batch" and not training) else NormRoute.GENERIC
+        self._norm_fwd(sv, a, y, out, cout, act, training)
 
     # ---- fused latent heads: mu = conv1x1(x), sigma = softplus(conv1x1(x)), z = mu + sigma * eps (posteriors.py:125-128,
     # priors.py:117-120) as one launch forward (phx_latent_heads_fwd) and one backward (phx_latent_heads_bwd) ----------------------
@@ -283,51 +347,54 @@ class ForwardLowering:
         return True
 
     def _fw_conv_unit(self, op, bw):
+        """conv -> [bias] -> [norm] -> act: prepare the operands, choose the normalisation route (conv_norm_route), emit that route."""
         a = op.attrs
         if a.get("transposed") is not None or a.get("general") is not None:
             return self._fw_tconv_unit(op, bw)
         if op in self._norm_head:                # its forward ran inside the producer's apply pass
-            x = self.val[op.inputs[0]]
-            W = a["W"]
-            self.saved[op] = dict(x=x, out=self.val[op.outputs[0]], mfma=False, norm=None, padded=False, cin_eff=W.shape[-2], k1=False,
-                                  head1x1=True, norm_head=True)
+            self.saved[op] = ConvSaved.plain(self.val[op.inputs[0]], self.val[op.outputs[0]], None, a["W"].shape[-2], head1x1=True, norm_head=True)
             return
         rec = self._lat.get(op)
         if rec is not None:                      # a latent head: its arithmetic runs in the group's one launch
             self.val[op.outputs[0]] = self._alloc_like(op.outputs[0])
-            self.saved[op] = dict(latent=True)
+            self.saved[op] = ConvSaved.plain(None, self.val[op.outputs[0]], None, a["W"].shape[-2], latent=True)
             if rec["last"] is op:
                 self._fw_latent_group(rec)
             return
+        o = self._conv_operands(op, bw)
+        sv = self.saved[op] = o.sv
+        if sv.norm is None:
+            self._conv_into(o, o.out, o.act)
+            return
+        o.y = self._alloc(o.out.shape, o.out.dt)
+        self._norm_vectors(sv, o.B, o.H * o.Wd, o.cout, a["num_groups"])
+        nv = a["norm_vars"]
+        o.params = (self.store.ptr(nv["gamma"]), self.store.ptr(nv["beta"]), tfnorm.EPS[sv.norm])
+        o.moving = self._moving_args(nv, sv.norm == "batch" and o.training and self.loss is not None)
+        sv.route, o.stats = conv_norm_route(self.L, sv.norm, o.training, bw, self.act_dt, o.x.dt, o.y.dt, o.out.dt, o.B, o.H, o.Wd, sv.cin_eff,
+                                            o.cout, sv.G, sv.mfma, sv.head1x1, o.dual is not None, o.up is not None)
+        getattr(self, "_fw_unit_" + sv.route.name.lower())(o, sv)
+        if sv.route is not NormRoute.INFER_FOLDED:
+            sv.y = o.y
+
+    def _conv_operands(self, op, bw):
+        """Classify a plain conv unit's convolution (bf16 MFMA as it is / channel-padded / 1x1 head / fp32 MFMA / direct; concat-free,
+        phase-form or unmaterialised input), pad its input where needed and look up its packed filter -> the operand record the
+        launch methods take (_fw_conv_unit and the normalisation route add y, params, moving, stats, sums, pivot, apply_args)."""
+        a = op.attrs
         x = self.val[op.inputs[0]]
         W, b = a["W"], a["b"]
         k, (_, _, cin, cout) = a["ksize"], W.shape
         B, H, Wd = x.shape[0], x.shape[1], x.shape[2]
         out = self._alloc_like(op.outputs[0])
         self.val[op.outputs[0]] = out
-        act = rt.ACT_CODES[a["act"]]
-        training = a["training"] if isinstance(a["training"], bool) else self.training
         mfma = (self.act_dt == BF16 and x.dt == BF16 and out.dt == BF16 and k == 3 and cin % 32 == 0
                 and cout % 32 == 0)
-        S, Lb = self.stream, self.L
         dual = x if isinstance(x, DualBuf) else None
         assert dual is None or mfma, "concat-free input reached a convolution off the MFMA path"
         up = x if isinstance(x, UpBuf) else None      # bilinear_upsample2D of up.src, never written: this unit runs in the phase form (upconv.py)
         xf = x if isinstance(x, XfBuf) else None      # the producer's activation was never written: this launch re-forms it (see _xf_edge_ok)
         assert xf is None or (mfma and a["norm"] == "batch" and b is None), "unmaterialised activation reached a convolution that cannot re-form it"
-
-        def mfma_conv(y, bias_p, oscale_p, act_code, stats, stats_mode, ws, wsb):
-            """One forward launch on the bf16 MFMA path (plain or concat-free input): phx_conv3x3_mfma_bf16_dual takes every option"""
-            if xf is not None:
-                assert bias_p is None and oscale_p is None and act_code == 0 and stats_mode in (0, 1) and ws is None
-                self._emit(Lb.conv3x3_mfma_bf16_xf, xf.y.ptr, xf.scale.ptr, xf.shift.ptr, wf.ptr, y.ptr,
-                           stats.ptr if stats is not None else None, B, H, Wd, cin_eff, cout, S,
-                           tag="conv3x3_mfma_fwd", flops=18.0 * cin * cout * B * H * Wd)
-                return
-            self._emit(Lb.conv3x3_mfma_bf16_dual, x.ptr, dual.b.ptr if dual is not None else None, dual.k1 if dual is not None else 0,
-                       wf.ptr, y.ptr if y is not None else None, None, 0, bias_p, oscale_p, act_code,
-                       stats.ptr if stats is not None else None, stats_mode, ws.ptr if ws is not None else None, wsb,
-                       B, H, Wd, cin_eff, cout, S, tag="conv3x3_mfma_fwd", flops=18.0 * cin * cout * B * H * Wd)
         cin_eff = cin
         # Convolutions the 3x3 MFMA kernels do not take as they are: input channels not a multiple of 32 (image Cin = 1 / 3,
         # latent Cin = 2, prob_unet2D's feature + z concat) are zero-padded, and 1x1 filters (prob_unet2D's recombination
@@ -340,239 +407,238 @@ class ForwardLowering:
             cin_eff = (cin + 31) // 32 * 32
             if cin_eff != cin or x.dt != BF16:        # (with cin_eff == cin the pad kernel is just the cast to bf16)
                 xp = self._alloc((B, H, Wd, cin_eff), BF16)
-                self._emit(Lb.pad_channels_bf16, x.ptr, x.dt, cin, xp.ptr, cin_eff, B * H * Wd, S)
+                self._emit(self.L.pad_channels_bf16, x.ptr, x.dt, cin, xp.ptr, cin_eff, B * H * Wd, self.stream)
                 x = xp
             mfma = True
-        st = dict(x=x, out=out, mfma=mfma, norm=a["norm"], padded=padded, cin_eff=cin_eff, k1=bool(padded and k1))
-        wptr, bptr = self.store.ptr(W), (self.store.ptr(b) if b is not None else None)
-        if padded:
-            wf = self._alloc((9 * cin_eff * cout,), BF16)
-            need_dgrad = bw and self.req.get(op.inputs[0], False)
-            wdp = self._alloc((9 * cin_eff * cout,), BF16) if need_dgrad else None
-            st["wd_pad"] = wdp
-            self._pack_jobs.append((wptr, wf.ptr, wdp.ptr if wdp else 0, cin, cin_eff, cout, 1 if k1 else 0))
-        elif mfma:
-            wf, _ = self._packed(W)
-
         head1x1 = (k == 1 and out.dt == F32 and cout in (2, 4, 6, 8) and a["norm"] is None and b is not None)
-        st["head1x1"] = head1x1
         # fp32 plans: the 3x3 convolution on the fp32 matrix instruction (same arithmetic class as the direct kernel: an fp32 FMA chain)
         f32m = bool(not mfma and self.act_dt == F32 and x.dt == F32 and out.dt == F32 and k == 3 and cout % 32 == 0 and _f32_mfma_enabled()
-                    and isinstance(x, Buf) and Lb.conv3x3_f32_mfma_supported(B, H, Wd, cin, cout))
-        st["f32m"] = f32m
+                    and isinstance(x, Buf) and self.L.conv3x3_f32_mfma_supported(B, H, Wd, cin, cout))
+        sv = ConvSaved(x, out, a["norm"], mfma, padded, cin_eff, bool(padded and k1), head1x1, f32m=f32m)
+        wptr, wf = self.store.ptr(W), None
+        if padded:
+            wf = self._alloc((9 * cin_eff * cout,), BF16)
+            sv.wd_pad = self._alloc((9 * cin_eff * cout,), BF16) if (bw and self.req.get(op.inputs[0], False)) else None
+            self._pack_jobs.append((wptr, wf.ptr, sv.wd_pad.ptr if sv.wd_pad else 0, cin, cin_eff, cout, 1 if k1 else 0))
+        elif mfma:
+            wf, _ = self._packed(W)
+        return types.SimpleNamespace(op=op, a=a, bw=bw, sv=sv, x=x, out=out, W=W, k=k, cin=cin, cout=cout, B=B, H=H, Wd=Wd, dual=dual, up=up, xf=xf,
+                                     wf=wf, wptr=wptr, bptr=self.store.ptr(b) if b is not None else None, act=rt.ACT_CODES[a["act"]],
+                                     training=a["training"] if isinstance(a["training"], bool) else self.training,
+                                     y=None, sums=None, pivot=None, stats=None, apply_args=None)
 
-        def tiles_fn():
-            if dual is not None:
-                return int(Lb.conv3x3_mfma_bf16_tiles_dual(B, H, Wd, cin_eff, cout))
-            return int(Lb.conv3x3_mfma_bf16_tiles(B, H, Wd, cin_eff, cout))
+    def _mfma_conv(self, o, y, bias_p, oscale_p, act_code, stats, stats_mode, ws, wsb):
+        """One forward launch on the bf16 MFMA path (plain or concat-free input): phx_conv3x3_mfma_bf16_dual takes every option"""
+        Lb, x, xf, dual = self.L, o.x, o.xf, o.dual
+        geo = (o.B, o.H, o.Wd, o.sv.cin_eff, o.cout, self.stream)
+        flops = 18.0 * o.cin * o.cout * o.B * o.H * o.Wd
+        if xf is not None:
+            assert bias_p is None and oscale_p is None and act_code == 0 and stats_mode in (0, 1) and ws is None
+            self._emit(Lb.conv3x3_mfma_bf16_xf, xf.y.ptr, xf.scale.ptr, xf.shift.ptr, o.wf.ptr, y.ptr,
+                       stats.ptr if stats is not None else None, *geo, tag="conv3x3_mfma_fwd", flops=flops)
+            return
+        self._emit(Lb.conv3x3_mfma_bf16_dual, x.ptr, dual.b.ptr if dual is not None else None, dual.k1 if dual is not None else 0,
+                   o.wf.ptr, y.ptr if y is not None else None, None, 0, bias_p, oscale_p, act_code,
+                   stats.ptr if stats is not None else None, stats_mode, ws.ptr if ws is not None else None, wsb,
+                   *geo, tag="conv3x3_mfma_fwd", flops=flops)
 
-        def conv_into(y, act_code, stats_direct=None, stats_part=None, stats_atomic=None):
-            if up is not None:
-                # y <- the hi-res pre-normalisation map in PACKED pixel order [B, h, w, (a, b, cout)]: the per-channel norm kernels do not
-                # care about the order of the pixels; the apply pass's output is permuted to hi-res below
-                assert act_code == 0 and stats_direct is None and stats_part is None and stats_atomic is None
-                st["upconv"] = upconv.forward(self._emit, self._alloc, Lb, S, up.src, wptr, wf, y, B, H // 2, Wd // 2, cin, cout,
-                                              need_dgrad=bool(bw and self.req.get(op.inputs[0].op.inputs[0], False)), bias_ptr=bptr)
-                return
-            if stats_atomic is not None:
-                mfma_conv(y, bptr, None, act_code, stats_atomic, 2, None, 0)
-            elif head1x1:
-                self._emit(Lb.head1x1_fwd, x.ptr, x.dt, wptr, bptr, y.ptr, B * H * Wd, cin, cout, act_code, S)
-            elif mfma:
-                wsb = int(Lb.conv3x3_mfma_ws_bytes(B, H, Wd, cin_eff, cout)) if stats_part is None else 0
-                ws = self._alloc((wsb // 4,), F32) if wsb else None          # split-K slices (small maps)
-                mfma_conv(y, bptr, None, act_code, stats_part, 1 if stats_part is not None else 0, ws, wsb)
-            elif f32m and stats_direct is None and y.dt == F32:
-                need_dgrad = bool(bw and self.req.get(op.inputs[0], False) and cin % 32 == 0)
-                w32, _ = self._packed_f32(W, need_dgrad)
-                self._emit(Lb.conv3x3_f32_mfma, x.ptr, w32.ptr, bptr, y.ptr, B, H, Wd, cin, cout, act_code, S,
-                           tag="conv3x3_f32_mfma_fwd", flops=18.0 * cin * cout * B * H * Wd)
+    def _conv_tiles(self, o):
+        tiles = self.L.conv3x3_mfma_bf16_tiles_dual if o.dual is not None else self.L.conv3x3_mfma_bf16_tiles
+        return int(tiles(o.B, o.H, o.Wd, o.sv.cin_eff, o.cout))
+
+    def _conv_into(self, o, y, act_code, stats_direct=None, stats_part=None, stats_atomic=None):
+        """The unit's convolution (+ bias, + activation `act_code`) into y on whichever kernel its operands select."""
+        S, Lb, x, sv, op = self.stream, self.L, o.x, o.sv, o.op
+        B, H, Wd, cin, cout = o.B, o.H, o.Wd, o.cin, o.cout
+        if o.up is not None:
+            # y <- the hi-res pre-normalisation map in PACKED pixel order [B, h, w, (a, b, cout)]: the per-channel norm kernels do not
+            # care about the order of the pixels; the apply pass's output is permuted to hi-res below
+            assert act_code == 0 and stats_direct is None and stats_part is None and stats_atomic is None
+            sv.upconv = upconv.forward(self._emit, self._alloc, Lb, S, o.up.src, o.wptr, o.wf, y, B, H // 2, Wd // 2, cin, cout,
+                                       need_dgrad=bool(o.bw and self.req.get(op.inputs[0].op.inputs[0], False)), bias_ptr=o.bptr)
+        elif stats_atomic is not None:
+            self._mfma_conv(o, y, o.bptr, None, act_code, stats_atomic, 2, None, 0)
+        elif sv.head1x1:
+            self._emit(Lb.head1x1_fwd, x.ptr, x.dt, o.wptr, o.bptr, y.ptr, B * H * Wd, cin, cout, act_code, S)
+        elif sv.mfma:
+            wsb = int(Lb.conv3x3_mfma_ws_bytes(B, H, Wd, sv.cin_eff, cout)) if stats_part is None else 0
+            ws = self._alloc((wsb // 4,), F32) if wsb else None          # split-K slices (small maps)
+            self._mfma_conv(o, y, o.bptr, None, act_code, stats_part, 1 if stats_part is not None else 0, ws, wsb)
+        elif sv.f32m and stats_direct is None and y.dt == F32:
+            need_dgrad = bool(o.bw and self.req.get(op.inputs[0], False) and cin % 32 == 0)
+            w32, _ = self._packed_f32(o.W, need_dgrad)
+            self._emit(Lb.conv3x3_f32_mfma, x.ptr, w32.ptr, o.bptr, y.ptr, B, H, Wd, cin, cout, act_code, S,
+                       tag="conv3x3_f32_mfma_fwd", flops=18.0 * cin * cout * B * H * Wd)
+        else:
+            self._emit(Lb.conv2d_direct, x.ptr, x.dt, o.wptr, o.bptr, y.ptr, y.dt, B, H, Wd, cin, cout, o.k, act_code,
+                       0, stats_direct.ptr if stats_direct is not None else None, S)
+
+    # ---- one emitter per normalisation route (NormRoute; the table is in DESIGN.md section 1) ------------------------------------
+    def _fw_unit_infer_folded(self, o, sv):
+        # inference-mode batch norm + activation folded into the convolution's epilogue (phx_conv3x3_mfma_bf16_affine):
+        # one launch where the reference runs conv2d, batch_norm and relu; the scale / shift vectors of all layers come
+        # from one launch at the head of the run
+        nv = o.a["norm_vars"]
+        gptr, beptr, eps = o.params
+        self._bninfer_jobs.append((gptr, beptr, self.store.ptr(nv["moving_mean"]), self.store.ptr(nv["moving_variance"]),
+                                   sv.scale.ptr, sv.shift.ptr, o.cout, eps))
+        wsb = int(self.L.conv3x3_mfma_ws_bytes(o.B, o.H, o.Wd, sv.cin_eff, o.cout))
+        ws = self._alloc((wsb // 4,), F32) if wsb else None
+        self._mfma_conv(o, o.out, sv.shift.ptr, sv.scale.ptr, o.act, None, 0, ws, wsb)
+
+    def _fw_unit_infer(self, o, sv):
+        self._norm_fwd(sv, o.a, o.y, o.out, o.cout, o.act, o.training, conv=lambda: self._conv_into(o, o.y, 0))
+
+    def _conv_f32out(self, o, sum_slices):
+        """The 2 x 2 / 4 x 4 levels: the pre-normalisation tensor stays in fp32 (the split-K kernel's accumulators, summed) --
+        a channel is normalised from a few dozen to a few hundred values here, and the bf16 rounding of y (2^-9 of the
+        channel mean) is blown up with their spread: the two coarsest KL terms trained 40 % high.
+        -> (workspace of slices, slice count)"""
+        Lb, dual, geo = self.L, o.dual, (o.B, o.H, o.Wd, o.sv.cin_eff, o.cout)
+        o.y = self._alloc(o.out.shape, F32)
+        wsb = int(Lb.conv3x3_mfma_ws_bytes(*geo))
+        ws = self._alloc((wsb // 4,), F32) if wsb else None
+        self._emit(Lb.conv3x3_mfma_bf16_f32out, o.x.ptr, dual.b.ptr if dual is not None else None,
+                   dual.k1 if dual is not None else 0, o.wf.ptr, o.y.ptr, sum_slices, ws.ptr if ws is not None else None, wsb,
+                   *geo, self.stream, tag="conv3x3_mfma_fwd", flops=18.0 * o.cin * o.cout * o.B * o.H * o.Wd)
+        return ws, int(Lb.conv3x3_mfma_ksplit(*geo))
+
+    def _fw_unit_bn_wide(self, o, sv):
+        # the batch-norm launch is the split-K finishing pass as well (phx_bn_wide_fwd: four channels per block,
+        # sums the slices in slice order): one launch fewer per layer, 48 blocks instead of 12 on a 192-channel layer
+        # (a block of that launch pulls P x nz 128-byte lines through ONE CU whatever its channel count: measured + 5 us per
+        # layer at 2 x 2 (P = 256, six slices), - 8 us at 4 x 4 (P = 1 024, three slices) against finishing pass + phx_bn_small_fwd)
+        ws, nz = self._conv_f32out(o, 0)
+        y, out = o.y, o.out
+        self._emit(self.L.bn_wide_fwd, ws.ptr if nz > 1 else y.ptr, nz, y.ptr, *o.params, out.ptr, sv.mean.ptr, sv.rstd.ptr,
+                   sv.scale.ptr, sv.shift.ptr, *o.moving, sv.P, o.cout, o.act,
+                   self.stream, tag="bytes_norm_apply", flops=float(y.nbytes + out.nbytes))
+
+    def _fw_unit_bn_small(self, o, sv):
+        # H <= 8 levels: the whole batch-norm layer in one launch (phx_bn_small_fwd / _bwd; csrc/elementwise.hip)
+        # (policy P <= 1024, the H <= 4 levels: at P = 4096 the single launch measured no faster than the chain)
+        if sv.route is NormRoute.BN_SMALL_F32Y:
+            self._conv_f32out(o, 1)
+        else:
+            self._conv_into(o, o.y, 0)
+        y, out = o.y, o.out
+        self._emit(self.L.bn_small_fwd, y.ptr, y.dt, *o.params, out.ptr, sv.mean.ptr, sv.rstd.ptr, sv.scale.ptr, sv.shift.ptr,
+                   *o.moving, sv.P, o.cout, o.act, self.stream,
+                   tag="bytes_norm_apply", flops=float(y.nbytes + out.nbytes))
+
+    _fw_unit_bn_small_f32y = _fw_unit_bn_small
+
+    def _fw_unit_fgn(self, o, sv):
+        # maps of at most 16 x 16: convolution, bias, group / instance norm and activation in ONE launch (a block holds whole
+        # samples and whole groups: no cross-block step); the backward pass is phx_norm_small_bwd's
+        self._emit(self.L.conv3x3_mfma_bf16_fgn, o.x.ptr, o.wf.ptr, o.y.ptr, o.out.ptr, o.bptr, *o.params, sv.G, o.act,
+                   sv.mean.ptr, sv.rstd.ptr, sv.scale.ptr, sv.shift.ptr, o.B, o.H, o.Wd, sv.cin_eff, o.cout, self.stream,
+                   tag="conv3x3_mfma_fwd", flops=18.0 * o.cin * o.cout * o.B * o.H * o.Wd, shape=("fgn", o.B, o.H, o.Wd, sv.cin_eff, o.cout))
+
+    def _fw_unit_norm_small(self, o, sv):
+        # group / instance norm on maps of up to 256 pixels: the whole layer in one launch as well (phx_norm_small_fwd / _bwd: a
+        # wave per (sample, 16-channel slice)); a split-K convolution hands over its slices and its bias
+        self._conv_into(o, o.y, 0)
+        y, out = o.y, o.out
+        self._emit(self.L.norm_small_fwd, y.ptr, None, 0, None, *o.params, out.ptr, sv.mean.ptr, sv.rstd.ptr,
+                   sv.scale.ptr, sv.shift.ptr, sv.NS, sv.P, o.cout, sv.G, o.act, self.stream,
+                   tag="bytes_norm_apply", flops=float(y.nbytes + out.nbytes))
+
+    def _fw_unit_generic(self, o, sv):
+        """Statistics from o.stats (StatsSource), then the first apply-pass variant that takes the unit."""
+        o.sums = self._alloc_zeroed(sv.NS * o.cout * 2)
+        self._conv_with_stats(o, sv)
+        o.apply_args = self._norm_apply_args(sv, o.a, o.y, o.sums, o.pivot, o.out, o.cout, o.act, o.training)
+        for apply in (self._apply_xf, self._apply_d2s, self._apply_head, self._apply_pool, self._apply_plain):
+            if apply(o, sv):
+                break
+        if sv.norm != "batch":
+            sv.fsums, sv.fpivot = o.sums, o.pivot         # forward per-channel sums: the bias gradient is closed-form from them
+
+    def _conv_with_stats(self, o, sv):
+        """The convolution into o.y with the per-channel sums in o.sums: shifted (pivot) sums in a stand-alone pass -- always on the
+        fp32 parity path, and on the bf16 path when a statistic has few samples (cheap there) -- otherwise from the conv epilogue."""
+        Lb, S, y, src = self.L, self.stream, o.y, o.stats
+        if src is StatsSource.PIVOT_PASS:
+            # (phase form: the frame of the packed map is written after the phase convolution: its statistics epilogue cannot be used)
+            o.pivot = self._norm_stats_pass(sv, y, o.sums, o.cout, conv=lambda: self._conv_into(o, y, 0))
+        elif src is StatsSource.ATOMIC:
+            # few pixel tiles (the H <= 16 levels): the convolution adds its statistics straight into `sums` -- no pass over y
+            self._conv_into(o, y, 0, stats_atomic=o.sums)
+        elif src is StatsSource.DIRECT:
+            self._conv_into(o, y, 0, stats_direct=o.sums)        # (direct kernels add their tiles' sums atomically)
+        else:
+            ntile = self._conv_tiles(o)
+            part = self._alloc((ntile * 2 * o.cout,), F32)
+            self._conv_into(o, y, 0, stats_part=part)
+            if src is StatsSource.PARTIALS:
+                self._emit(Lb.norm_reduce_partials, part.ptr, ntile, o.cout, o.sums.ptr, S)
             else:
-                self._emit(Lb.conv2d_direct, x.ptr, x.dt, wptr, bptr, y.ptr, y.dt, B, H, Wd, cin, cout, k, act_code,
-                           0, stats_direct.ptr if stats_direct is not None else None, S)
-
-        norm = a["norm"]
-        if norm is None:
-            conv_into(out, act)
-            self.saved[op] = st
-            return
-        nv = a["norm_vars"]
-        gptr, beptr = self.store.ptr(nv["gamma"]), self.store.ptr(nv["beta"])
-        y = self._alloc(out.shape, out.dt)
-        if norm == "batch":
-            NS, P, Gn = 1, B * H * Wd, cout
-        else:
-            Gn = cout if norm == "instance" else (a["num_groups"] or max(2, cout // 16))
-            NS, P = B, H * Wd
-        scale, shift = self._alloc((NS * cout,), F32), self._alloc((NS * cout,), F32)
-        mean, rstd = self._alloc((NS * Gn,), F32), self._alloc((NS * Gn,), F32)
-        eps = tfnorm.EPS[norm]
-        if norm == "batch" and not training and mfma and not head1x1 and not bw:
-            # inference-mode batch norm + activation folded into the convolution's epilogue (phx_conv3x3_mfma_bf16_affine):
-            # one launch where the reference runs conv2d, batch_norm and relu; the scale / shift vectors of all layers come
-            # from one launch at the head of the run
-            self._bninfer_jobs.append((gptr, beptr, self.store.ptr(nv["moving_mean"]), self.store.ptr(nv["moving_variance"]),
-                                       scale.ptr, shift.ptr, cout, eps))
-            wsb = int(Lb.conv3x3_mfma_ws_bytes(B, H, Wd, cin_eff, cout))
-            ws = self._alloc((wsb // 4,), F32) if wsb else None
-            mfma_conv(out, shift.ptr, scale.ptr, act, None, 0, ws, wsb)
-            st.update(scale=scale, shift=shift, NS=NS, P=P, G=Gn)
-            self.saved[op] = st
-            return
-        if norm == "batch" and not training:
-            self._emit(Lb.bn_infer_scale_shift, gptr, beptr, self.store.ptr(nv["moving_mean"]),
-                       self.store.ptr(nv["moving_variance"]), eps, cout, scale.ptr, shift.ptr, S)
-            conv_into(y, 0)
-            self._emit(Lb.affine_act, y.ptr, y.dt, scale.ptr, shift.ptr, out.ptr, out.dt, NS, P, cout, act, S)
-        else:
-            # H <= 8 levels: the whole batch-norm layer in one launch (phx_bn_small_fwd / _bwd; csrc/elementwise.hip)
-            # (policy P <= 1024, the H <= 4 levels: at P = 4096 the single launch measured no faster than the chain)
-            bn_small = (norm == "batch" and y.dt == BF16 and out.dt == BF16 and P <= _BN_SMALL
-                        and Lb.bn_small_supported(P, cout, BF16))
-            if bn_small:
-                upd = training and self.loss is not None
-                mm = self.store.ptr(nv["moving_mean"]) if upd else None
-                mv = self.store.ptr(nv["moving_variance"]) if upd else None
-                mom = (1.0 - tfnorm.BN_DECAY) if upd else 0.0
-                if mfma and not head1x1 and _BN_SMALL_F32 and Lb.conv3x3_mfma_f32out_supported(B, H, Wd, cin_eff, cout):
-                    # the 2 x 2 / 4 x 4 levels: the pre-normalisation tensor stays in fp32 (the split-K kernel's accumulators, summed) --
-                    # a channel is normalised from a few dozen to a few hundred values here, and the bf16 rounding of y (2^-9 of the
-                    # channel mean) is blown up with their spread: the two coarsest KL terms trained 40 % high
-                    y = self._alloc(out.shape, F32)
-                    wsb = int(Lb.conv3x3_mfma_ws_bytes(B, H, Wd, cin_eff, cout))
-                    ws = self._alloc((wsb // 4,), F32) if wsb else None
-                    nz = int(Lb.conv3x3_mfma_ksplit(B, H, Wd, cin_eff, cout))
-                    # ... and the batch-norm launch is the split-K finishing pass as well (phx_bn_wide_fwd: four channels per block,
-                    # sums the slices in slice order): one launch fewer per layer, 48 blocks instead of 12 on a 192-channel layer
-                    # (a block of that launch pulls P x nz 128-byte lines through ONE CU whatever its channel count: measured + 5 us per
-                    # layer at 2 x 2 (P = 256, six slices), - 8 us at 4 x 4 (P = 1 024, three slices) against finishing pass + phx_bn_small_fwd)
-                    wide = bool(_BN_WIDE and Lb.bn_wide_supported(P, cout) and P * nz <= _BN_WIDE_MAXLINES)
-                    self._emit(Lb.conv3x3_mfma_bf16_f32out, x.ptr, dual.b.ptr if dual is not None else None,
-                               dual.k1 if dual is not None else 0, wf.ptr, y.ptr, 0 if wide else 1, ws.ptr if ws is not None else None, wsb,
-                               B, H, Wd, cin_eff, cout, S, tag="conv3x3_mfma_fwd", flops=18.0 * cin * cout * B * H * Wd)
-                    if wide:
-                        self._emit(Lb.bn_wide_fwd, ws.ptr if nz > 1 else y.ptr, nz, y.ptr, gptr, beptr, eps, out.ptr, mean.ptr, rstd.ptr,
-                                   scale.ptr, shift.ptr, mm, mv, mom, P, cout, act, S,
-                                   tag="bytes_norm_apply", flops=float(y.nbytes + out.nbytes))
-                        st.update(y=y, scale=scale, shift=shift, mean=mean, rstd=rstd, NS=NS, P=P, G=Gn, bn_small=True, bn_wide=True)
-                        self.saved[op] = st
-                        return
-                else:
-                    conv_into(y, 0)
-                self._emit(Lb.bn_small_fwd, y.ptr, y.dt, gptr, beptr, eps, out.ptr, mean.ptr, rstd.ptr, scale.ptr, shift.ptr,
-                           mm, mv, mom, P, cout, act, S,
-                           tag="bytes_norm_apply", flops=float(y.nbytes + out.nbytes))
-                st.update(y=y, scale=scale, shift=shift, mean=mean, rstd=rstd, NS=NS, P=P, G=Gn, bn_small=True)
-                self.saved[op] = st
-                return
-            if (norm != "batch" and mfma and not head1x1 and dual is None and not _DETERMINISTIC and (_fgn_mode() >= 2 or (_fgn_mode() == 1 and Gn != cout)) and y.dt == BF16 and out.dt == BF16
-                    and x.dt == BF16 and Lb.conv3x3_fgn_supported(B, H, Wd, cin_eff, cout, Gn)
-                    and Lb.norm_small_supported(NS, P, cout, Gn, BF16)):
-                # maps of at most 16 x 16: convolution, bias, group / instance norm and activation in ONE launch (a block holds whole
-                # samples and whole groups: no cross-block step); the backward pass is phx_norm_small_bwd's
-                self._emit(Lb.conv3x3_mfma_bf16_fgn, x.ptr, wf.ptr, y.ptr, out.ptr, bptr, gptr, beptr, eps, Gn, act, mean.ptr, rstd.ptr,
-                           scale.ptr, shift.ptr, B, H, Wd, cin_eff, cout, S,
-                           tag="conv3x3_mfma_fwd", flops=18.0 * cin * cout * B * H * Wd, shape=("fgn", B, H, Wd, cin_eff, cout))
-                st.update(y=y, scale=scale, shift=shift, mean=mean, rstd=rstd, NS=NS, P=P, G=Gn, norm_small=True)
-                self.saved[op] = st
-                return
-            # group / instance norm on maps of up to 256 pixels: the whole layer in one launch as well (phx_norm_small_fwd / _bwd: a
-            # wave per (sample, 16-channel slice)); a split-K convolution hands over its slices and its bias
-            if (norm != "batch" and y.dt == BF16 and out.dt == BF16
-                    and Lb.norm_small_supported(NS, P, cout, Gn, BF16)):
-                conv_into(y, 0)
-                self._emit(Lb.norm_small_fwd, y.ptr, None, 0, None, gptr, beptr, eps, out.ptr, mean.ptr, rstd.ptr,
-                           scale.ptr, shift.ptr, NS, P, cout, Gn, act, S,
-                           tag="bytes_norm_apply", flops=float(y.nbytes + out.nbytes))
-                st.update(y=y, scale=scale, shift=shift, mean=mean, rstd=rstd, NS=NS, P=P, G=Gn, norm_small=True)
-                self.saved[op] = st
-                return
-            sums = self._alloc_zeroed(NS * cout * 2)
-            pivot = None
-            # shifted (pivot) sums in a stand-alone pass: always on the fp32 parity path, and on the bf16 path when
-            # a statistic has few samples (cheap there); otherwise the sums come from the conv epilogue.
-            small = P <= 16384 or self.act_dt == F32
-            xf_producer_ok = False
-            if up is not None:
-                # (the frame of the packed map is written after the phase convolution: its statistics epilogue cannot be used)
-                pivot = self._alloc((NS * cout,), F32)
-                conv_into(y, 0)
-                self._emit(Lb.norm_stats, y.ptr, y.dt, sums.ptr, pivot.ptr, NS, P, cout, S)
-            elif norm == "batch" and mfma and not small:
-                ntile = tiles_fn()
-                part = self._alloc((ntile * 2 * cout,), F32)
-                conv_into(y, 0, stats_part=part)
-                self._emit(Lb.norm_reduce_partials, part.ptr, ntile, cout, sums.ptr, S)
-                xf_producer_ok = bool(training and act == rt.ACT_RELU and y.dt == BF16 and out.dt == BF16 and not head1x1 and _xf_enabled())
-            elif (norm == "batch" and mfma and small and not _DETERMINISTIC and not head1x1 and self.act_dt == BF16
-                  and Lb.conv3x3_mfma_stats_atomic_supported(B, H, Wd, cin_eff, cout)):
-                # few pixel tiles (the H <= 16 levels): the convolution adds its statistics straight into `sums` -- no pass over y
-                conv_into(y, 0, stats_atomic=sums)
-            elif (norm != "batch" and mfma and not head1x1 and self.act_dt == BF16 and H % 16 == 0 and Wd % 16 == 0
-                  and tiles_fn() % B == 0):
                 # group / instance norm on maps of at least 16 x 16: a pixel tile lies inside one sample, so the convolution's per-tile
                 # sums reduce to per-sample sums without another pass over y (phx_norm_reduce_partials_ns)
-                ntile = tiles_fn()
-                part = self._alloc((ntile * 2 * cout,), F32)
-                conv_into(y, 0, stats_part=part)
-                self._emit(Lb.norm_reduce_partials_ns, part.ptr, ntile // B, B, cout, sums.ptr, S)
-            elif norm == "batch" and not small and not _DETERMINISTIC:
-                conv_into(y, 0, stats_direct=sums)        # (direct kernels add their tiles' sums atomically)
-            else:
-                pivot = self._alloc((NS * cout,), F32)
-                conv_into(y, 0)
-                self._emit(Lb.norm_stats, y.ptr, y.dt, sums.ptr, pivot.ptr, NS, P, cout, S)
-            upd = norm == "batch" and training and self.loss is not None
-            mmp = self.store.ptr(nv["moving_mean"]) if upd else None
-            mvp = self.store.ptr(nv["moving_variance"]) if upd else None
-            mom = (1.0 - tfnorm.BN_DECAY) if upd else 0.0
-            if (bw and xf_producer_ok and pivot is None and self._xf_edge_ok(op, B, H, Wd, cout)):
-                # every reader of a = relu(bn(y)) is a large-map 3x3 convolution (and its filter gradient): no apply pass, no tensor a --
-                # the statistics are finalised by a one-block launch and the readers transform y in their loaders (XfBuf)
-                self._emit(Lb.norm_finalize, sums.ptr, None, gptr, beptr, eps, NS, P, cout, Gn, mean.ptr, rstd.ptr, scale.ptr, shift.ptr,
-                           mmp, mvp, mom, S)
-                self.val[op.outputs[0]] = XfBuf(out, y, scale, shift)
-                st.update(y=y, scale=scale, shift=shift, mean=mean, rstd=rstd, NS=NS, P=P, G=Gn, out=None)
-                self.saved[op] = st
-                return
-            apply_args = (y.ptr, y.dt, sums.ptr, pivot.ptr if pivot is not None else None, gptr, beptr, eps, out.ptr, out.dt,
-                          mean.ptr, rstd.ptr, scale.ptr, shift.ptr, mmp, mvp, mom, NS, P, cout, Gn, act)
-            hop = self._norm_head_consumer(op) if (y.dt == BF16 and out.dt == BF16 and up is None) else None
-            if up is not None:
-                # y is in the packed pixel order, the readers of a want hi-res rows: the apply pass writes them (depth-to-space on the fly)
-                self._emit(Lb.norm_apply_fused_d2s, *apply_args[:16], NS, P, cout, Gn, act, H // 2, Wd // 2, S, tag="bytes_norm_apply",
-                           flops=float(y.nbytes + out.nbytes))
-            elif hop is not None and Lb.norm_head_supported(cout, hop.attrs["W"].shape[-1], y.dt, out.dt):
-                # the head rides on the apply pass (phx_norm_apply_fused_head): no pass of its own over a
-                hW, hb = hop.attrs["W"], hop.attrs["b"]
-                yh = self._alloc_like(hop.outputs[0])
-                self.val[hop.outputs[0]] = yh
-                # training plan, batch norm: a itself is never written -- its one other reader, the head's filter gradient (a leaf of the
-                # backward graph), re-forms it from y with this layer's scale / shift (phx_head1x1_wgrad_multi, xscale): for the
-                # likelihood's top layer (128 channels @ 128 x 128) 268 MB less to write on the critical lane
-                skip_a = bool(bw and norm == "batch" and NS == 1 and _SKIP_HEAD_A)
-                if skip_a:
-                    apply_args = apply_args[:7] + (None,) + apply_args[8:]
-                    st["a_unwritten"] = dict(y=y, scale=scale, shift=shift, act=act)
-                self._emit(Lb.norm_apply_fused_head, *apply_args, self.store.ptr(hW), self.store.ptr(hb), hW.shape[-1], yh.ptr, S,
-                           tag="bytes_norm_apply", flops=float(y.nbytes + (0 if skip_a else out.nbytes)))
-                self._norm_head[hop] = op
-            else:
-                pop = self._pool_consumer(op, H, Wd, cout) if (y.dt == BF16 and out.dt == BF16) else None
-                if pop is not None:
-                    # one of the readers is averagepool2D (the next encoder level): the apply pass writes the pooled tensor too
-                    pooled = self._alloc(self._cshape(pop.outputs[0]), out.dt)
-                    self.val[pop.outputs[0]] = pooled
-                    self._pool_done.add(pop)
-                    self._emit(Lb.norm_apply_pool, y.ptr, sums.ptr, pivot.ptr if pivot is not None else None, gptr, beptr, eps, out.ptr,
-                               pooled.ptr, mean.ptr, rstd.ptr, scale.ptr, shift.ptr, mmp, mvp, mom, NS, P, cout, Gn, H, Wd, act, S,
-                               tag="bytes_norm_apply", flops=float(y.nbytes + out.nbytes + pooled.nbytes))
-                else:
-                    self._emit(Lb.norm_apply_fused, *apply_args, S, tag="bytes_norm_apply", flops=float(y.nbytes + out.nbytes))
-        st.update(y=y, scale=scale, shift=shift, mean=mean, rstd=rstd, NS=NS, P=P, G=Gn)
-        if norm != "batch":
-            st.update(fsums=sums, fpivot=pivot)          # forward per-channel sums: the bias gradient is closed-form from them
-        self.saved[op] = st
+                self._emit(Lb.norm_reduce_partials_ns, part.ptr, ntile // o.B, o.B, o.cout, o.sums.ptr, S)
+
+    def _apply_xf(self, o, sv):
+        """Every reader of a = relu(bn(y)) is a large-map 3x3 convolution (and its filter gradient): no apply pass, no tensor a --
+        the statistics are finalised by a one-block launch and the readers transform y in their loaders (XfBuf)."""
+        y, out = o.y, o.out
+        if not (o.bw and o.stats is StatsSource.PARTIALS and o.training and o.act == rt.ACT_RELU and y.dt == BF16 and out.dt == BF16
+                and not sv.head1x1 and _xf_enabled() and self._xf_edge_ok(o.op, o.B, o.H, o.Wd, o.cout)):
+            return False
+        self._emit(self.L.norm_finalize, o.sums.ptr, None, *o.params, sv.NS, sv.P, o.cout, sv.G, sv.mean.ptr, sv.rstd.ptr,
+                   sv.scale.ptr, sv.shift.ptr, *o.moving, self.stream)
+        self.val[o.op.outputs[0]] = XfBuf(out, y, sv.scale, sv.shift)
+        sv.out = None
+        return True
+
+    def _apply_d2s(self, o, sv):
+        """Phase form: y is in the packed pixel order, the readers of a want hi-res rows: the apply pass writes them (depth-to-space
+        on the fly)."""
+        if o.up is None:
+            return False
+        self._emit(self.L.norm_apply_fused_d2s, *o.apply_args, o.H // 2, o.Wd // 2, self.stream, tag="bytes_norm_apply",
+                   flops=float(o.y.nbytes + o.out.nbytes))
+        return True
+
+    def _apply_head(self, o, sv):
+        """The unit's only reader is a 1x1 head: it rides on the apply pass (phx_norm_apply_fused_head), no pass of its own over a."""
+        y, out, op = o.y, o.out, o.op
+        hop = self._norm_head_consumer(op) if (y.dt == BF16 and out.dt == BF16) else None
+        if hop is None or not self.L.norm_head_supported(o.cout, hop.attrs["W"].shape[-1], y.dt, out.dt):
+            return False
+        hW, hb = hop.attrs["W"], hop.attrs["b"]
+        yh = self._alloc_like(hop.outputs[0])
+        self.val[hop.outputs[0]] = yh
+        # training plan, batch norm: a itself is never written -- its one other reader, the head's filter gradient (a leaf of the
+        # backward graph), re-forms it from y with this layer's scale / shift (phx_head1x1_wgrad_multi, xscale): for the
+        # likelihood's top layer (128 channels @ 128 x 128) 268 MB less to write on the critical lane
+        skip_a = bool(o.bw and sv.norm == "batch" and sv.NS == 1 and _SKIP_HEAD_A)
+        args = o.apply_args
+        if skip_a:
+            args = args[:7] + (None,) + args[8:]
+            sv.a_unwritten = dict(y=y, scale=sv.scale, shift=sv.shift, act=o.act)
+        self._emit(self.L.norm_apply_fused_head, *args, self.store.ptr(hW), self.store.ptr(hb), hW.shape[-1], yh.ptr, self.stream,
+                   tag="bytes_norm_apply", flops=float(y.nbytes + (0 if skip_a else out.nbytes)))
+        self._norm_head[hop] = op
+        return True
+
+    def _apply_pool(self, o, sv):
+        """One of the readers is averagepool2D (the next encoder level): the apply pass writes the pooled tensor too."""
+        y, out = o.y, o.out
+        pop = self._pool_consumer(o.op, o.H, o.Wd, o.cout) if (y.dt == BF16 and out.dt == BF16) else None
+        if pop is None:
+            return False
+        pooled = self._alloc(self._cshape(pop.outputs[0]), out.dt)
+        self.val[pop.outputs[0]] = pooled
+        self._pool_done.add(pop)
+        self._emit(self.L.norm_apply_pool, y.ptr, o.sums.ptr, o.pivot.ptr if o.pivot is not None else None, *o.params, out.ptr,
+                   pooled.ptr, sv.mean.ptr, sv.rstd.ptr, sv.scale.ptr, sv.shift.ptr, *o.moving, sv.NS, sv.P, o.cout, sv.G, o.H, o.Wd, o.act,
+                   self.stream, tag="bytes_norm_apply", flops=float(y.nbytes + out.nbytes + pooled.nbytes))
+        return True
+
+    def _apply_plain(self, o, sv):
+        self._emit(self.L.norm_apply_fused, *o.apply_args, self.stream, tag="bytes_norm_apply", flops=float(o.y.nbytes + o.out.nbytes))
+        return True
 
     def _fw_maxpool(self, op, bw):
         x = self.val[op.inputs[0]]
@@ -628,40 +694,17 @@ class ForwardLowering:
         act = rt.ACT_CODES[a["act"]]
         norm = a["norm"]
         training = a["training"] if isinstance(a["training"], bool) else self.training
-        S, Lb = self.stream, self.L
+        sv = self.saved[op] = ConvSaved.plain(x, out, norm, C)
         if norm is None:
             ones = Buf((C,), F32, like=torch.ones(C, dtype=torch.float32, device=_device()))
             zeros = Buf((C,), F32, like=torch.zeros(C, dtype=torch.float32, device=_device()))
             self._keep += [ones, zeros]
-            self._emit(Lb.affine_act, x.ptr, x.dt, ones.ptr, zeros.ptr, out.ptr, out.dt, 1, B * HW, C, act, S)
-            self.saved[op] = dict(norm=None, out=out)
+            self._emit(self.L.affine_act, x.ptr, x.dt, ones.ptr, zeros.ptr, out.ptr, out.dt, 1, B * HW, C, act, self.stream)
             return
-        nv = a["norm_vars"]
-        gptr, beptr = self.store.ptr(nv["gamma"]), self.store.ptr(nv["beta"])
-        if norm == "batch":
-            NS, P, Gn = 1, B * HW, C
-        else:
-            Gn = C if norm == "instance" else (a["num_groups"] or max(2, C // 16))
-            NS, P = B, HW
-        scale, shift = self._alloc((NS * C,), F32), self._alloc((NS * C,), F32)
-        mean, rstd = self._alloc((NS * Gn,), F32), self._alloc((NS * Gn,), F32)
-        eps = tfnorm.EPS[norm]
-        st = dict(norm=norm, y=x, out=out, scale=scale, shift=shift, mean=mean, rstd=rstd, NS=NS, P=P, G=Gn)
-        if norm == "batch" and not training:
-            self._emit(Lb.bn_infer_scale_shift, gptr, beptr, self.store.ptr(nv["moving_mean"]),
-                       self.store.ptr(nv["moving_variance"]), eps, C, scale.ptr, shift.ptr, S)
-            self._emit(Lb.affine_act, x.ptr, x.dt, scale.ptr, shift.ptr, out.ptr, out.dt, NS, P, C, act, S)
-            st["inference"] = True
-        else:
-            sums = self._alloc_zeroed(NS * C * 2)
-            pivot = self._alloc((NS * C,), F32)
-            self._emit(Lb.norm_stats, x.ptr, x.dt, sums.ptr, pivot.ptr, NS, P, C, S)
-            upd = norm == "batch" and training and self.loss is not None
-            self._emit(Lb.norm_apply_fused, x.ptr, x.dt, sums.ptr, pivot.ptr, gptr, beptr, eps, out.ptr, out.dt, mean.ptr, rstd.ptr,
-                       scale.ptr, shift.ptr, self.store.ptr(nv["moving_mean"]) if upd else None,
-                       self.store.ptr(nv["moving_variance"]) if upd else None, (1.0 - tfnorm.BN_DECAY) if upd else 0.0,
-                       NS, P, C, Gn, act, S)
-        self.saved[op] = st
+        sv.y = x
+        self._norm_vectors(sv, B, HW, C, a["num_groups"])
+        sv.route = NormRoute.INFER if (norm == "batch" and not training) else NormRoute.GENERIC
+        self._norm_fwd(sv, a, x, out, C, act, training)
 
     def _fw_flatten(self, op, bw):
         x = self.val[op.inputs[0]]

@@ -140,6 +140,53 @@ def test_launch_plans_host_side():
     assert L.conv3x3_mfma_stats_atomic_supported(64, 16, 16, 192, 192) == 1 and L.conv3x3_mfma_stats_atomic_supported(64, 128, 128, 32, 32) == 0
 
 
+def test_conv_unit_route_table():
+    """engine_forward.conv_norm_route (pure: library queries + plain values) at the layer shapes of the benchmarked network, batch 64
+    and 2: bf16, training with backward, 3x3, ReLU, plain input, not a head.  Shapes are (H = W, Cin, Cout).  And the saved record
+    the routes are stored in refuses attributes it does not declare."""
+    from phiseg_code_amd import runtime as rt
+    from phiseg_code_amd.engine_common import BF16, ConvSaved, NormRoute as R, StatsSource as S
+    from phiseg_code_amd.engine_forward import conv_norm_route
+    L = rt.lib()
+
+    def route(norm, B, shape, det=False, fgn=1):
+        H, cin, cout = shape
+        Gn = max(2, cout // 16) if norm == "group" else cout
+        return conv_norm_route(L, norm, True, True, BF16, BF16, BF16, BF16, B, H, H, cin, cout, Gn, True, False, False, False,
+                               deterministic=det, fgn=fgn)
+    part, atom, pivot, part_ns = (R.GENERIC, S.PARTIALS), (R.GENERIC, S.ATOMIC), (R.GENERIC, S.PIVOT_PASS), (R.GENERIC, S.PARTIALS_NS)
+    f32y, wide = (R.BN_SMALL_F32Y, None), (R.BN_WIDE, None)
+    batch_norm = {64: [((128, 32, 32), part, part), ((64, 32, 64), part, part), ((64, 64, 64), part, part), ((32, 64, 128), part, part),
+                       ((32, 128, 128), part, part), ((16, 128, 192), atom, pivot), ((16, 192, 192), atom, pivot), ((8, 192, 192), atom, pivot),
+                       ((8, 384, 192), atom, pivot), ((4, 192, 192), f32y, f32y), ((2, 384, 192), f32y, f32y), ((2, 192, 192), wide, wide),
+                       ((4, 64, 192), wide, wide)],
+                  2: [((128, 32, 32), part, part), ((64, 32, 64), atom, pivot), ((64, 64, 64), atom, pivot), ((32, 64, 128), atom, pivot),
+                      ((32, 128, 128), atom, pivot), ((16, 192, 192), f32y, f32y), ((16, 128, 192), wide, wide), ((8, 192, 192), wide, wide),
+                      ((8, 384, 192), wide, wide), ((4, 192, 192), wide, wide), ((2, 192, 192), wide, wide), ((2, 384, 192), wide, wide),
+                      ((4, 64, 192), wide, wide)]}
+    for B, rows in batch_norm.items():
+        for shape, default, det in rows:
+            assert route("batch", B, shape) == default, ("batch", B, shape)
+            assert route("batch", B, shape, det=True) == det, ("batch, deterministic", B, shape)
+    large = [(128, 32, 32), (64, 32, 64), (64, 64, 64), (32, 64, 128), (32, 128, 128)]
+    small = [(16, 128, 192), (16, 192, 192), (8, 192, 192), (8, 384, 192), (4, 192, 192), (2, 192, 192)]
+    for B in (64, 2):
+        for shape in large:
+            for norm, kw in (("group", {}), ("group", dict(det=True)), ("group", dict(fgn=0)), ("instance", {})):
+                assert route(norm, B, shape, **kw) == part_ns, (norm, kw, B, shape)
+        for shape in small:
+            assert route("group", B, shape) == (R.FGN, None), ("group", B, shape)
+            assert route("group", B, shape, det=True) == (R.NORM_SMALL, None), ("group, deterministic", B, shape)
+            assert route("group", B, shape, fgn=0) == (R.NORM_SMALL, None), ("group, PHX_FGN=0", B, shape)
+            assert route("instance", B, shape) == (R.NORM_SMALL, None), ("instance", B, shape)
+    sv = ConvSaved.plain(None, None, "batch", 32)
+    assert sv.route is R.NONE and sv.y is None and sv.f32m is False
+    with pytest.raises(AttributeError):
+        sv.bn_wide
+    with pytest.raises(AttributeError):
+        sv.bn_wide = True
+
+
 @pytest.mark.parametrize("shape", [(64, 16, 16, 384, 384), (64, 16, 16, 768, 384), (64, 32, 32, 384, 384), (12, 16, 16, 512, 512),
                                    (64, 16, 16, 384, 192), (64, 64, 64, 192, 192), (64, 32, 32, 128, 128)])
 def test_deferred_filter_gradient_job_fits_the_stand_alone_workspace(shape):
