@@ -563,6 +563,38 @@ int phx_mc_stats(const float* logits, const float* sm, const unsigned char* gt, 
 /* eval_xent (phiseg_model.py:111) of one graph instance: out[p] = logsumexp(logits[p][:]) - logits[p][labels[p]], npix pixels */
 int phx_softmax_xent_map(const float* logits, const unsigned char* labels, float* out, size_t npix, int C, void* stream);
 
+/* ---- TensorBoard summaries on the device (phiseg_model.py:199-203, 704-818; tfwrapper/layers.py:671-677; csrc/summary.hip) -------
+ * phx_summary_histograms: what tf.summary.histogram computes on the host, for a LIST of segments in one launch (+ a memset and an
+ * nseg-thread finishing launch).  TensorFlow 1.12's default buckets (core/lib/histogram/histogram.cc): the caller builds the 1551
+ * limits on the host ("v = 1e-12; while v < 1e20: push(v); v *= 1.1" in double, then DBL_MAX; negated and reversed, 0.0, the
+ * positives) and passes them as `limits` (device); a value is widened to double and counted in bucket upper_bound(limits, v), exactly.
+ *   segs   [nseg] DEVICE table of phx_summary_segment (device pointer, element count, PHX_F32 / PHX_BF16); max_n = the largest n
+ *   counts [nseg][PHX_SUMMARY_BUCKETS] u64, stats [nseg][PHX_SUMMARY_NSTATS] f64 (PHX_SUMMARY_* below): both overwritten
+ *   min / max / num cover the FINITE values and are exact (0 for a segment without any); sum / sum_squares are double sums whose
+ *   order varies from run to run; NaN and +-Inf are counted in PHX_SUMMARY_NONFINITE and in no bucket
+ *   work   scratch of phx_summary_histograms_ws_bytes(nseg) bytes */
+enum { PHX_SUMMARY_BUCKETS = 1551 };
+enum { PHX_SUMMARY_MIN = 0, PHX_SUMMARY_MAX = 1, PHX_SUMMARY_NUM = 2, PHX_SUMMARY_SUM = 3, PHX_SUMMARY_SUM_SQUARES = 4,
+       PHX_SUMMARY_NONFINITE = 5, PHX_SUMMARY_NSTATS = 8 };
+typedef struct phx_summary_segment {
+    const void* ptr;
+    unsigned long long n;
+    int dtype;
+    int reserved;
+} phx_summary_segment;              /* 24 bytes */
+size_t phx_summary_histograms_ws_bytes(int nseg);
+int phx_summary_histograms(const phx_summary_segment* segs, int nseg, uint64_t max_n, const double* limits, unsigned long long* counts,
+                           double* stats, void* work, size_t work_bytes, void* stream);
+/* put_kernels_on_grid (tfwrapper/utils.py:93-168) of one batch: src -> the uint8 image out[(H + 2) * grid_y][(W + 2) * grid_x], tile
+ * of image b at row block b % grid_y, column block b / grid_y, a zero pad of 1 around every tile.  form: PHX_GRID_LOGITS_F32
+ * [B,H,W,C] f32 (arg-max over C, first maximum wins), PHX_GRID_LABELS_U8 [B,H,W] u8, PHX_GRID_IMAGE_F32 [B,H,W] f32.  Pixel value:
+ * the reference's 'image' branch in fp32, (v - min) / max * 254 with min / max of the whole batch (reduced in this call), truncated;
+ * NaN -> 0 and values outside [0, 255] saturate (tf.cast is undefined there).  shift: src is a nearest-neighbour view stored at
+ * (H >> shift) x (W >> shift).  work: PHX_SUMMARY_GRID_WS_BYTES bytes of scratch. */
+enum { PHX_GRID_LOGITS_F32 = 0, PHX_GRID_LABELS_U8 = 1, PHX_GRID_IMAGE_F32 = 2, PHX_SUMMARY_GRID_WS_BYTES = 8 };
+int phx_summary_grid_u8(const void* src, int form, int B, int H, int W, int C, int shift, int grid_y, int grid_x, unsigned char* out,
+                        void* work, void* stream);
+
 /* ---- transposed convolution (tfwrapper/layers.py:197-258, tf.nn.conv2d_transpose) --------------
  * x [B,H,W,Cin] -> y [B, H*sh, W*sw, Cout], filter w_hwoi [kh][kw][Cout][Cin] fp32 (TF's layout), SAME padding, optional bias and
  * activation.  dgrad: dy [B, H*sh, W*sw, Cout] -> dx [B,H,W,Cin].  wgrad ACCUMULATES into dw_hwoi.  Direct (untuned) kernels: no

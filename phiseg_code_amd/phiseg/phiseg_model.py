@@ -300,11 +300,16 @@ class phiseg():
         if self._is_writer():
             os.makedirs(self.log_dir, exist_ok=True)
 
-    def train(self, data, num_iter=None, log_every=100, log_dir=None):
+    def train(self, data, num_iter=None, log_every=100, log_dir=None, summaries=False):
         """The reference's train(data) (phiseg_model.py:166-207): continue mode, lr schedule, one ELBO step per iteration,
-        `_do_validation` (checkpoint + metrics + best-of checkpoints) every `validation_frequency` steps.  TensorBoard
-        summaries (199-203) are out of scope.  `log_dir=None` keeps everything in memory (no checkpoints, no validation)
-        unless the config's log root exists; pass a directory to get the reference's on-disk behaviour.
+        `_do_validation` (checkpoint + metrics + best-of checkpoints) every `validation_frequency` steps.  `log_dir=None` keeps
+        everything in memory (no checkpoints, no validation); pass a directory to get the reference's on-disk behaviour.
+        summaries=True (with a log_dir): the reference's TensorBoard summaries (199-203, 662-701, 704-818) go to ONE event file
+        events.out.tfevents.<time>.<host> in the log dir (phiseg_code_amd/summary.py) -- every `tensorboard_update_frequency` steps the
+        loss, the learning rate, the mean of every mu / sigma, a histogram of every filter, bias and conv unit's activations and (with
+        `do_image_summaries`) the image grids, from one inference-mode run on the batch just trained on; at every validation the
+        train / validation loss terms, Dice, GED, NCC and the val_* / generated_* grids.  The summary run reads the parameters and
+        writes nothing the training step reads: losses are the same with and without it.  Off (the default): no event file, no extra plan.
         Data-parallel: `data` should draw rank-dependent batches (SyntheticLIDC(cfg, seed=1234 + rank)); the returned /
         logged loss is the global-batch mean; only rank 0 writes files."""
         cfg = self.exp_config
@@ -316,6 +321,19 @@ class phiseg():
             if self.continue_run:
                 self.load_weights(self.init_checkpoint_path)
         self.best_dice, self.best_loss, self.best_ged, self.best_ncc = -1, np.inf, np.inf, -1
+        self._summary_writer = None
+        if summaries and on_disk and self._is_writer():
+            from phiseg_code_amd import summary
+            self._summary_writer = summary.EventFileWriter(self.log_dir)
+        try:
+            return self._train_loop(data, num_iter, log_every, on_disk)
+        finally:
+            if self._summary_writer is not None:
+                self._summary_writer.close()
+                self._summary_writer = None
+
+    def _train_loop(self, data, num_iter, log_every, on_disk):
+        cfg = self.exp_config
         losses = []
         t0 = time.time()
         for step in range(self.init_step, num_iter):
@@ -330,10 +348,155 @@ class phiseg():
                 world = self.dist.world if (self.dist is not None and self.dist.active) else 1
                 logging.info('step %d  loss %.4f  (%.1f img/s)', step, losses[-1],
                              (step - self.init_step + 1) * cfg.batch_size * world / max(time.time() - t0, 1e-9))
+            if self._summary_writer is not None and step % cfg.tensorboard_update_frequency == 0:
+                self._write_training_summary(step, x_b, s_b, lr)
             vf = getattr(cfg, 'validation_frequency', None)
             if on_disk and vf and step % vf == 0:
                 self._do_validation(data)
         return losses
+
+    # ---- TensorBoard summaries (phiseg_model.py:199-203, 662-701, 704-818) -----------------------------------
+    def _summary_spec(self):
+        """What one summary run fetches, built once: the loss, every mu / sigma, the output levels, s_accum, and the output of every
+        conv unit the loss depends on (the never-consumed up-sampling branches, SURVEY.md Q1, and the generation-mode prior / the
+        evaluation likelihood are not reachable from loss_tot: the reference histograms their activations too, we do not)."""
+        if getattr(self, '_summary_spec_cache', None) is None:
+            L = self.exp_config.latent_levels
+            seen, stack = set(), [self.loss_tot.op]
+            while stack:
+                op = stack.pop()
+                if op not in seen:
+                    seen.add(op)
+                    stack.extend(i.op for i in op.inputs)
+            units, used = [], {}
+            for op in self.graph.ops:
+                if op in seen and op.type == 'conv_unit':
+                    w = op.attrs['W'].name
+                    scope = w[:-2] if w.endswith('/W') else op.name          # the unit's variable scope (tf: the layer's name scope)
+                    k = used.get(scope, 0)
+                    used[scope] = k + 1
+                    units.append(((scope if k == 0 else '%s_%d' % (scope, k)) + '/activations', op.outputs[0]))
+            scalars = []
+            for ii in range(L):
+                scalars += [('average_mu_lvl%d' % ii, self.mu_list[ii]), ('average_sigma_lvl%d' % ii, self.sigma_list[ii]),
+                            ('average_prior_mu_lvl%d' % ii, self.prior_mu_list[ii]), ('average_prior_sigma_lvl%d' % ii, self.prior_sigma_list[ii])]
+            scalars = [(tag, t) for tag, t in scalars if isinstance(t, G.Tensor) and len(t.shape) > 0]
+            # s_accum[ii] = s_out_list[L-1] + ... + s_out_list[ii] (phiseg_model.py:245-258): level L-1 is the last output level itself,
+            # level 0 is self.s_out, the levels between are added to the graph here
+            s_out = self.s_out if self.s_out is not None else self._s_out_sum()
+            accum = []
+            for ii in range(L):
+                if ii == L - 1:
+                    accum.append(self.s_out_list[ii])
+                elif ii == 0:
+                    accum.append(s_out)
+                else:
+                    accum.append(self._lazy_node('s_accum_%d' % ii, lambda ii=ii: G.aggregate_logits(self.s_out_list[ii:])[0]))
+            images = [('s_out', s_out)] + [e for ii in range(L) for e in (('s_out_list_%d' % ii, self.s_out_list[ii]), ('s_accum_list_%d' % ii, accum[ii]))]
+            fetches = []
+            for t in [self.loss_tot] + [t for _, t in scalars] + [t for _, t in images] + [t for _, t in units]:
+                if not any(t is f for f in fetches):
+                    fetches.append(t)
+            self._summary_spec_cache = dict(units=units, scalars=scalars, images=images, fetches=fetches, hist={})
+        return self._summary_spec_cache
+
+    def _summary_run(self, x_b, s_b, lr, histograms):
+        """One inference-mode run of the summary plan on (x_b, s_b); behind the replay, on the plan's stream: one histogram call over the
+        activations and one over the parameter arena's filters and biases (histograms=True), and one grid launch per image summary.
+        -> (loss, {tag: (count row, stats row)} or None, [(name, uint8 grid)]).  Advances the sampling noise step, which no training
+        step reads (training plans key their noise by the optimiser step)."""
+        from phiseg_code_amd import runtime as rt
+        from phiseg_code_amd import summary
+        cfg = self.exp_config
+        spec = self._summary_spec()
+        fd = {self.x_inp: x_b, self.s_inp: s_b, self.training_pl: False}
+        if lr is not None:
+            fd[self.lr_pl] = lr
+        plan, _ = self.sess.run_buffers(spec['fetches'], fd)
+        stream = plan.stream
+        hist = None
+        if histograms:
+            if id(plan) not in spec['hist']:
+                store = self.sess._ensure_store()
+                # the activations, then any mu / sigma that is not itself a conv unit's output (its mean comes from the same call)
+                segs = list(spec['units']) + [(tag, t) for tag, t in spec['scalars'] if not any(t is u for _, u in spec['units'])]
+                seg_t, seg_tags = [t for _, t in segs], [tag for tag, _ in segs]
+                bufs = [plan.val[t] for t in seg_t]
+                act = summary.Histogrammer([(b.ptr, b.n, b.dt) for b in bufs])
+                pvars = [v for name, v in self.graph.variables.items() if v.trainable and (name.endswith('/W') or name.endswith('/b'))]
+                par = summary.Histogrammer([(store.ptr(v), v.size, rt.F32) for v in pvars])
+                spec['hist'][id(plan)] = (act, seg_t, seg_tags, par, [v.name + '_0' for v in pvars])       # (tf: '<name>:0' -> '<name>_0')
+            act, seg_t, seg_tags, par, par_tags = spec['hist'][id(plan)]
+            act.run(stream)
+            par.run(stream)
+        grids = []
+        if getattr(cfg, 'do_image_summaries', False):
+            B = int(np.asarray(x_b).shape[0])
+            xb, sb = plan.feeds['x_input'], plan.feeds['s_input']
+            H, W = xb.shape[1], xb.shape[2]
+            grids.append(('x_inp', summary.grid_u8_device(xb.ptr, summary.GRID_IMAGE_F32, B, H, W, 1, stream)))
+            grids.append(('s_inp', summary.grid_u8_device(sb.ptr, summary.GRID_LABELS_U8, B, H, W, 1, stream)))
+            for name, t in spec['images']:
+                b = plan.val[t]
+                grids.append((name, summary.grid_u8_device(b.ptr, summary.GRID_LOGITS_F32, B, H, W, b.shape[-1], stream, shift=b.shift)))
+        plan.sync()
+        world = self.dist.world if (self.dist is not None and self.dist.active) else 1
+        loss = float(plan.fetch(self.loss_tot)) * world        # (data parallel: the writer rank's share of the global mean -> its batch's loss)
+        if histograms:
+            a_counts, a_stats = act.result(stream)
+            p_counts, p_stats = par.result(stream)
+            summary.check_finite(par_tags, p_stats)
+            summary.check_finite(seg_tags, a_stats)
+            hist = dict(par=(par_tags, p_counts, p_stats), act=([tag for tag, _ in spec['units']], a_counts, a_stats), seg_t=seg_t)
+        grids = [(name, g.cpu().numpy()) for name, g in grids]
+        self._advance_noise()
+        return loss, hist, grids
+
+    def _write_training_summary(self, step, x_b, s_b, lr):
+        """phiseg_model.py:199-203: sess.run(self.summary, {x_inp, s_inp, training_pl: False, lr_pl}) + add_summary + flush"""
+        from phiseg_code_amd import summary as S
+        loss, hist, grids = self._summary_run(x_b, s_b, lr, histograms=True)
+        spec = self._summary_spec()
+        values = [S.scalar_value('batch_total_loss', loss), S.scalar_value('learning_rate', lr)]
+        _, a_counts, a_stats = hist['act']
+        for tag, t in spec['scalars']:
+            st = a_stats[[i for i, u in enumerate(hist['seg_t']) if u is t][0]]
+            values.append(S.scalar_value(tag, st[S.STAT_SUM] / max(st[S.STAT_NUM], 1.0)))
+        for tags, counts, stats in (hist['par'], hist['act']):
+            for i, tag in enumerate(tags):
+                st = stats[i]
+                values.append(S.histogram_value(tag, st[S.STAT_MIN], st[S.STAT_MAX], st[S.STAT_NUM], st[S.STAT_SUM], st[S.STAT_SUM_SQUARES], counts[i]))
+        values += [S.image_value('train_%s/image/0' % name, g) for name, g in grids]
+        self._summary_writer.add_summary(values, step)
+        self._summary_writer.flush()
+
+    def _write_validation_summary(self, global_step, names, val_out, train_out, out, val_batch):
+        """phiseg_model.py:662-701: the validation summary (loss terms of the validation batch, Dice / ELBO / GED / NCC, the val_* and
+        generated_* grids) and the train summary (loss terms of a training batch), both at global_step."""
+        from phiseg_code_amd import summary as S
+        cfg = self.exp_config
+        values = [S.scalar_value('val_batch_%s' % n, v) for n, v in zip(names, val_out)]
+        if val_batch is not None and getattr(cfg, 'do_image_summaries', False):
+            val_x, val_s = val_batch
+            _, _, grids = self._summary_run(val_x, val_s, None, histograms=False)
+            values += [S.image_value('val_%s/image/0' % name, g) for name, g in grids]
+            B = int(np.asarray(val_x).shape[0])
+            plan, (lg,) = self.sess.run_buffers([self.s_out_eval], {self.training_pl: False, self.x_inp: val_x})
+            xb = plan.feeds['x_input']
+            H, W = xb.shape[1], xb.shape[2]
+            seg = S.grid_u8_device(lg.ptr, S.GRID_LOGITS_F32, B, H, W, lg.shape[-1], plan.stream, shift=lg.shift)
+            xin = S.grid_u8_device(xb.ptr, S.GRID_IMAGE_F32, B, H, W, 1, plan.stream)
+            plan.sync()
+            values += [S.image_value('generated_seg/image/0', seg.cpu().numpy()), S.image_value('generated_x_in/image/0', xin.cpu().numpy())]
+            self._advance_noise()
+        psd = np.asarray(out['per_structure_dice']).reshape(-1)
+        values += [S.scalar_value('validation_dice_tot_score', out['dice']), S.scalar_value('validation_dice_mean_score', float(np.mean(psd)))]
+        values += [S.scalar_value('validation_dice_lbl_%d' % ii, psd[ii]) for ii in range(psd.size)]
+        values += [S.scalar_value('validation_neg_elbo', out['loss']), S.scalar_value('validation_GED', out['ged']),
+                   S.scalar_value('validation_NCC', out['ncc'])]
+        self._summary_writer.add_summary(values, global_step)
+        self._summary_writer.add_summary([S.scalar_value('train_batch_%s' % n, v) for n, v in zip(names, train_out)], global_step)
+        self._summary_writer.flush()
 
     # ---- validation (phiseg_model.py:530-660): N Monte-Carlo samples per image, metrics on the device ---------------
     def _do_validation(self, data):
@@ -357,9 +520,11 @@ class phiseg():
         if save:
             self.save_weights(os.path.join(self.log_dir, 'model.ckpt-%d' % global_step), format=self._ckpt_format(),
                               keep_prefix='model.ckpt', max_to_keep=1, average_state=False)
+        names, val_out, train_out, val_batch = [], [], [], None
         if hasattr(data.validation, 'next_batch'):                   # BATCH VALIDATION of every loss term (537-556)
             names = list(self.loss_dict.keys())
             val_x, val_s = data.validation.next_batch(cfg.batch_size)
+            val_batch = (val_x, val_s)
             val_out = self.sess.run(list(self.loss_dict.values()),
                                     feed_dict={self.x_inp: val_x, self.s_inp: val_s, self.training_pl: False})
             train_x, train_s = data.train.next_batch(cfg.batch_size)
@@ -413,6 +578,8 @@ class phiseg():
                 if save:                                               # (the reference: Saver(max_to_keep=2) per best-of saver)
                     self.save_weights(os.path.join(self.log_dir, 'model_best_%s.ckpt-%d' % (key, global_step)), format=self._ckpt_format(),
                                       keep_prefix='model_best_%s.ckpt' % key, max_to_keep=2, average_state=False)
+        if getattr(self, '_summary_writer', None) is not None:
+            self._write_validation_summary(global_step, names, val_out, train_out, out, val_batch)
         return out
 
     def _average_replica_state(self):

@@ -1,0 +1,331 @@
+"""TensorBoard event files without TensorFlow: what the reference's train() hands to tf.summary.FileWriter (phiseg_model.py:199-203,
+662-701, 704-818; tfwrapper/layers.py:671-677; tfwrapper/utils.py:93-168).
+
+Host side: the event-file writer and a reader of the same format, the protobuf wire encoding of Event / Summary / Summary.Value /
+Summary.Image / HistogramProto written by hand (as tfwrapper/tf_checkpoint.py does for tensor bundles), a zlib-only PNG encoder for
+8-bit grey images, and TensorFlow's default histogram bucket limits.  Device side: `Histogrammer` (phx_summary_histograms: every
+histogram of a summary in one launch, 12 KB per histogram travel to the host) and `grid_u8_device` (phx_summary_grid_u8:
+put_kernels_on_grid of one batch).  There is no host fallback for either.
+
+On-disk format (tensorflow/core/lib/io/record_writer.cc, tensorflow/core/util/events_writer.cc; restated -- TensorFlow is
+not a dependency and no file written here has been read by TensorBoard: parity is believed, not pinned):
+  file    events.out.tfevents.<unix seconds>.<hostname>, a sequence of records
+  record  uint64 length (little-endian) | uint32 masked CRC-32C of those 8 bytes | payload | uint32 masked CRC-32C of the payload
+  payload Event {1: wall_time double, 2: step int64, 3: file_version string | 5: Summary}; the first record carries
+          file_version "brain.Event:2"
+  Summary {1: repeated Value {1: tag, 2: simple_value float | 4: Image {1: height, 2: width, 3: colorspace, 4: encoded PNG}
+                               | 5: HistogramProto {1: min, 2: max, 3: num, 4: sum, 5: sum_squares, 6: packed bucket_limit, 7: packed bucket}}}
+"""
+import os
+import socket
+import struct
+import sys
+import time
+import zlib
+
+import numpy as np
+
+from phiseg_code_amd.tfwrapper.tf_checkpoint import _fields, crc32c, mask, put_varint, unmask
+
+N_LIMITS = 1551
+STAT_MIN, STAT_MAX, STAT_NUM, STAT_SUM, STAT_SUM_SQUARES, STAT_NONFINITE, N_STATS = 0, 1, 2, 3, 4, 5, 8     # PHX_SUMMARY_* (include/phx.h)
+GRID_LOGITS_F32, GRID_LABELS_U8, GRID_IMAGE_F32 = 0, 1, 2                                                   # PHX_GRID_*
+_limits = None
+
+
+def histogram_limits():
+    """TensorFlow's default histogram bucket limits (core/lib/histogram/histogram.cc, InitDefaultBucketsInner), built by the same loop
+    in double: 774 positive values 1e-12 * 1.1^k (by repeated multiplication) and DBL_MAX; the negated positives reversed, 0.0, the
+    positives -> 1551 limits.  A value belongs to the first bucket whose limit is strictly greater (std::upper_bound)."""
+    global _limits
+    if _limits is None:
+        pos = []
+        v = 1e-12
+        while v < 1e20:
+            pos.append(v)
+            v *= 1.1
+        pos.append(sys.float_info.max)
+        _limits = np.asarray([-p for p in reversed(pos)] + [0.0] + pos, dtype=np.float64)
+        _limits.setflags(write=False)
+        assert _limits.size == N_LIMITS
+    return _limits
+
+
+def factorization(n):
+    """tfwrapper/utils.py:109-114 of the reference: (grid_Y, grid_X) with grid_Y the largest divisor of n up to sqrt(n)"""
+    for i in range(int(np.sqrt(float(n))), 0, -1):
+        if n % i == 0:
+            return i, n // i
+
+
+# ---- protobuf wire encoding -------------------------------------------------------------------------------------------------
+def _key(num, wt):
+    return put_varint((num << 3) | wt)
+
+
+def _bytes_field(num, payload):
+    return _key(num, 2) + put_varint(len(payload)) + payload
+
+
+def _double_field(num, v):
+    return _key(num, 1) + struct.pack("<d", float(v))
+
+
+def _packed_doubles(num, vals):
+    return _bytes_field(num, np.asarray(vals, dtype="<f8").tobytes())
+
+
+def png_encode_gray8(img):
+    """[H, W] uint8 -> PNG bytes (8-bit greyscale, filter 0 on every row, one IDAT chunk; zlib only).  Compression level 1: a summary
+    holds a dozen 1040 x 1040 grids at the benchmark shape and level 6 spends 2 - 4x the host time on them for files 10 - 40 % smaller."""
+    a = np.ascontiguousarray(img, dtype=np.uint8)
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("png_encode_gray8: a non-empty [H, W] image, got shape %s" % (a.shape,))
+    h, w = a.shape
+    raw = np.zeros((h, w + 1), dtype=np.uint8)          # a filter-type byte (0 = none) in front of every scanline
+    raw[:, 1:] = a
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xffffffff)
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 0, 0, 0, 0)) +
+            chunk(b"IDAT", zlib.compress(raw.tobytes(), 1)) + chunk(b"IEND", b""))
+
+
+def scalar_value(tag, value):
+    """-> encoded Summary.Value {tag, simple_value}"""
+    return _bytes_field(1, tag.encode()) + _key(2, 5) + struct.pack("<f", float(value))
+
+
+def image_value(tag, img):
+    """[H, W] uint8 -> encoded Summary.Value {tag, image {height, width, colorspace 1 (greyscale), PNG}}"""
+    a = np.asarray(img)
+    png = png_encode_gray8(a)
+    im = _key(1, 0) + put_varint(a.shape[0]) + _key(2, 0) + put_varint(a.shape[1]) + _key(3, 0) + put_varint(1) + _bytes_field(4, png)
+    return _bytes_field(1, tag.encode()) + _bytes_field(4, im)
+
+
+def collapse_buckets(counts, limits=None):
+    """Histogram::EncodeToProto: every run of empty buckets becomes ONE entry that carries the run's last limit (count 0); a
+    non-empty bucket is an entry of its own.  -> (bucket_limit list, bucket list)"""
+    limits = histogram_limits() if limits is None else limits
+    counts = np.asarray(counts)
+    if counts.size == 0:
+        return [sys.float_info.max], [0.0]
+    full = counts > 0
+    keep = full | np.append(full[1:], True)          # a non-empty bucket, or the last bucket of a run of empty ones
+    return limits[:counts.size][keep].astype(np.float64).tolist(), counts[keep].astype(np.float64).tolist()
+
+
+def histogram_value(tag, hmin, hmax, num, hsum, sum_squares, counts):
+    """-> encoded Summary.Value {tag, histo}; counts: the 1551 default buckets (histogram_limits())"""
+    bl, bc = collapse_buckets(counts)
+    h = (_double_field(1, hmin) + _double_field(2, hmax) + _double_field(3, num) + _double_field(4, hsum) + _double_field(5, sum_squares) +
+         _packed_doubles(6, bl) + _packed_doubles(7, bc))
+    return _bytes_field(1, tag.encode()) + _bytes_field(5, h)
+
+
+def _record(payload):
+    head = struct.pack("<Q", len(payload))
+    return head + struct.pack("<I", mask(crc32c(head))) + payload + struct.pack("<I", mask(crc32c(payload)))
+
+
+class EventFileWriter:
+    """tf.summary.FileWriter's file: add_summary(values, step) appends one Event holding a Summary of the given encoded values
+    (scalar_value / image_value / histogram_value)."""
+
+    def __init__(self, log_dir, wall_time=None):
+        os.makedirs(log_dir, exist_ok=True)
+        t = time.time() if wall_time is None else wall_time
+        self.path = os.path.join(log_dir, "events.out.tfevents.%010d.%s" % (int(t), socket.gethostname()))
+        self._f = open(self.path, "ab")
+        self._f.write(_record(_double_field(1, t) + _bytes_field(3, b"brain.Event:2")))
+        self._f.flush()
+
+    def add_summary(self, values, step, wall_time=None):
+        summary = b"".join(_bytes_field(1, v) for v in values)
+        t = time.time() if wall_time is None else wall_time
+        self._f.write(_record(_double_field(1, t) + _key(2, 0) + put_varint(int(step)) + _bytes_field(5, summary)))
+
+    def flush(self):
+        self._f.flush()
+
+    def close(self):
+        if self._f is not None:
+            self._f.close()
+            self._f = None
+
+
+# ---- reader -------------------------------------------------------------------------------------------------------------------
+def _f64(v):
+    return struct.unpack("<d", struct.pack("<Q", v))[0]
+
+
+def _parse_value(buf):
+    out = {}
+    for num, wt, v in _fields(buf):
+        if num == 1:
+            out["tag"] = v.decode()
+        elif num == 2 and wt == 5:
+            out["simple_value"] = struct.unpack("<f", struct.pack("<I", v))[0]
+        elif num == 4:
+            im = {"height": 0, "width": 0, "colorspace": 0, "png": b""}
+            for n2, _, v2 in _fields(v):
+                if n2 in (1, 2, 3):
+                    im[("height", "width", "colorspace")[n2 - 1]] = v2
+                elif n2 == 4:
+                    im["png"] = v2
+            out["image"] = im
+        elif num == 5:
+            h = {"min": 0.0, "max": 0.0, "num": 0.0, "sum": 0.0, "sum_squares": 0.0, "bucket_limit": [], "bucket": []}
+            for n2, wt2, v2 in _fields(v):
+                if 1 <= n2 <= 5 and wt2 == 1:
+                    h[("min", "max", "num", "sum", "sum_squares")[n2 - 1]] = _f64(v2)
+                elif n2 in (6, 7):
+                    key = "bucket_limit" if n2 == 6 else "bucket"
+                    h[key].extend(np.frombuffer(v2, dtype="<f8").tolist() if wt2 == 2 else [_f64(v2)])
+            out["histo"] = h
+    return out
+
+
+def read_events(path, verify=True):
+    """Iterate the events of an event file: dicts {wall_time, step, file_version (first record), values: [{tag, simple_value | image |
+    histo}]}.  verify: check both CRCs of every record (ValueError on a mismatch or a truncated record)."""
+    buf = open(path, "rb").read()
+    pos = 0
+    while pos < len(buf):
+        if pos + 12 > len(buf):
+            raise ValueError("%s: truncated record header at byte %d" % (path, pos))
+        n = struct.unpack_from("<Q", buf, pos)[0]
+        if verify and unmask(struct.unpack_from("<I", buf, pos + 8)[0]) != crc32c(buf[pos:pos + 8]):
+            raise ValueError("%s: length checksum mismatch at byte %d" % (path, pos))
+        if pos + 12 + n + 4 > len(buf):
+            raise ValueError("%s: truncated record at byte %d" % (path, pos))
+        payload = buf[pos + 12:pos + 12 + n]
+        if verify and unmask(struct.unpack_from("<I", buf, pos + 12 + n)[0]) != crc32c(payload):
+            raise ValueError("%s: payload checksum mismatch at byte %d" % (path, pos))
+        pos += 12 + n + 4
+        ev = {"wall_time": 0.0, "step": 0, "file_version": None, "values": []}
+        for num, wt, v in _fields(payload):
+            if num == 1 and wt == 1:
+                ev["wall_time"] = _f64(v)
+            elif num == 2:
+                ev["step"] = v - (1 << 64) if v >= (1 << 63) else v
+            elif num == 3:
+                ev["file_version"] = v.decode()
+            elif num == 5:
+                ev["values"] = [_parse_value(v2) for n2, _, v2 in _fields(v) if n2 == 1]
+        yield ev
+
+
+def expand_buckets(histo):
+    """The 1551 default bucket counts of a parsed histo (the inverse of collapse_buckets: the collapsed runs were empty)."""
+    limits = histogram_limits()
+    counts = np.zeros(N_LIMITS, dtype=np.float64)
+    idx = np.searchsorted(limits, np.asarray(histo["bucket_limit"], dtype=np.float64), side="left")
+    counts[idx] = histo["bucket"]
+    return counts
+
+
+# ---- device side ----------------------------------------------------------------------------------------------------------------
+_SEG_DT = np.dtype([("ptr", "<u8"), ("n", "<u8"), ("dtype", "<i4"), ("reserved", "<i4")])      # phx_summary_segment
+_dev_limits = {}
+
+
+def _limits_on(dev):
+    import torch
+    if dev not in _dev_limits:
+        _dev_limits[dev] = torch.as_tensor(np.array(histogram_limits())).to(dev)
+    return _dev_limits[dev]
+
+
+class Histogrammer:
+    """The histograms of a FIXED list of device segments [(pointer, element count, runtime.F32 | BF16), ...]: the descriptor table
+    is uploaded once; run(stream) enqueues phx_summary_histograms behind whatever produced the segments on that stream; result()
+    copies the counts [nseg, 1551] (int64) and the statistics [nseg, 8] (float64) back."""
+
+    def __init__(self, segments):
+        import torch
+        from . import runtime as rt
+        self.L = rt.lib()
+        if not segments:
+            raise ValueError("Histogrammer: no segments")
+        tab = np.zeros(len(segments), dtype=_SEG_DT)
+        for i, (ptr, n, dt) in enumerate(segments):
+            if dt not in (rt.F32, rt.BF16):
+                raise ValueError("segment %d: dtype code %r is neither F32 nor BF16" % (i, dt))
+            tab[i] = (int(ptr), int(n), int(dt), 0)
+        self.nseg = len(segments)
+        self.max_n = int(tab["n"].max())
+        self.bytes_read = int(sum(int(n) * rt.DT_SIZE[dt] for _, n, dt in segments))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self.table = torch.as_tensor(tab.view(np.uint8)).to(dev)
+        self.limits = _limits_on(dev)
+        self.counts = torch.empty(self.nseg, N_LIMITS, dtype=torch.int64, device=dev)
+        self.stats = torch.empty(self.nseg, N_STATS, dtype=torch.float64, device=dev)
+        self.wsb = int(self.L.summary_histograms_ws_bytes(self.nseg))
+        self.work = torch.empty(max(self.wsb, 1), dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream().synchronize()          # uploaded on torch's stream, read on the caller's
+
+    def run(self, stream):
+        self.L.summary_histograms(self.table.data_ptr(), self.nseg, self.max_n, self.limits.data_ptr(), self.counts.data_ptr(),
+                                  self.stats.data_ptr(), self.work.data_ptr(), self.wsb, stream)
+
+    def result(self, stream):
+        self.L.stream_sync(stream)
+        return self.counts.cpu().numpy(), self.stats.cpu().numpy()
+
+
+def histograms(segments, stream=None):
+    """One phx_summary_histograms call over [(pointer, n, dtype code)] -> (counts [nseg, 1551] int64, stats [nseg, 8] float64)."""
+    import torch
+    h = Histogrammer(segments)
+    st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    h.run(st)
+    return h.result(st)
+
+
+def check_finite(tags, stats):
+    """tf.summary.histogram fails the run on a NaN or an Inf (HistogramSummary: 'Nan in summary histogram for: <tag>')"""
+    for tag, st in zip(tags, stats):
+        if st[STAT_NONFINITE] != 0:
+            raise FloatingPointError("Nan or Infinity in summary histogram for: %s (%d non-finite values)" % (tag, int(st[STAT_NONFINITE])))
+
+
+def grid_u8_device(ptr, form, B, H, W, C, stream, shift=0):
+    """Enqueue phx_summary_grid_u8 on `stream` -> the device uint8 tensor [(H + 2) * grid_Y, (W + 2) * grid_X] (NOT synchronised)."""
+    import torch
+    from . import runtime as rt
+    gy, gx = factorization(B)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    out = torch.empty((H + 2) * gy, (W + 2) * gx, dtype=torch.uint8, device=dev)
+    work = torch.empty(8, dtype=torch.uint8, device=dev)
+    rt.lib().summary_grid_u8(ptr, form, B, H, W, C, shift, gy, gx, out.data_ptr(), work.data_ptr(), stream)
+    out._phx_work = work                                   # (keeps the scratch alive until the grid is read)
+    return out
+
+
+def put_kernels_on_grid(images, batch_size=None, pad=1, min_int=None, max_int=None, **kwargs):
+    """tfwrapper/utils.py:93-168 of the reference for a host array: [B, X, Y] / [B, X, Y, 1] float images or uint8 label maps, or
+    [B, X, Y, C > 1] float logits (arg-max first) -> uint8 [1, (X + 2) * grid_Y, (Y + 2) * grid_X, 1].  Like the reference (whose
+    callers pass `rescale_mode`, a keyword it never reads) this always scales as (v - min) / max * 254."""
+    import torch
+    if pad != 1 or min_int or max_int or kwargs.get("mode", "image") != "image":
+        raise NotImplementedError("put_kernels_on_grid: pad=1 and the 'image' mode without fixed intensities (all the reference uses)")
+    a = np.asarray(images)
+    if a.ndim == 3:
+        a = a[..., None]
+    if a.ndim != 4:
+        raise ValueError("put_kernels_on_grid: [B, X, Y, C] expected, got shape %s" % (a.shape,))
+    B, H, W, C = a.shape
+    if batch_size is not None and int(batch_size) != B:
+        raise ValueError("put_kernels_on_grid: batch_size %s but %d images" % (batch_size, B))
+    if a.dtype == np.uint8 and C == 1:
+        form, host = GRID_LABELS_U8, a
+    else:
+        form, host = (GRID_IMAGE_F32 if C == 1 else GRID_LOGITS_F32), a.astype(np.float32)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    t = torch.as_tensor(np.ascontiguousarray(host)).to(dev)
+    st = torch.cuda.current_stream()
+    out = grid_u8_device(t.data_ptr(), form, B, H, W, C, st.cuda_stream)
+    st.synchronize()
+    return out.cpu().numpy()[None, :, :, None]

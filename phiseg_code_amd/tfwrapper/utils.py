@@ -96,6 +96,13 @@ def get_latest_model_checkpoint_path(folder, name):
     return os.path.join(folder, name + '-' + str(max(its)))
 
 
+def put_kernels_on_grid(images, batch_size, pad=1, min_int=None, max_int=None, **kwargs):
+    """tfwrapper/utils.py:93-168 of the reference: a batch arranged as one grid image, uint8 [1, (X + 2) * grid_Y, (Y + 2) * grid_X, 1],
+    formed on the device (phx_summary_grid_u8; phiseg_code_amd/summary.py)."""
+    from phiseg_code_amd import summary
+    return summary.put_kernels_on_grid(images, batch_size, pad=pad, min_int=min_int, max_int=max_int, **kwargs)
+
+
 def print_tensornames_in_checkpoint_file(file_name):
     """tfwrapper/utils.py:171-180 of the reference (pywrap_tensorflow.NewCheckpointReader there)."""
     from phiseg_code_amd.tfwrapper import tf_checkpoint
