@@ -462,6 +462,24 @@ int phx_global_avgpool_fwd(const float* x, float* y, int B, int P, int C, void* 
 int phx_global_avgpool_bwd(const float* dy, float* dx, int B, int P, int C, void* stream);
 int phx_broadcast_pixels_fwd(const float* z, void* out, int out_dt, int B, int P, int C, void* stream);
 int phx_broadcast_pixels_bwd(const void* dout, int dt, float* dz, int B, int P, int C, void* stream);
+/* prob_unet2D's recombination chain for n samples per image, one launch, inference mode (likelihoods.py:147-157: z broadcast over the
+ * image, concatenated behind the U-Net's features, three 1x1 conv units, the 1x1 prediction head [, soft-max]):
+ *   feat   [B][P][KF] PHX_BF16 | PHX_F32: the U-Net's feature map, NOT tiled (read once per pixel tile, shared by its samples).  KF = 32 or
+ *          64: the decoder's last level is 2 n0 wide (likelihoods.py:143-145), the recombination layers n0 = K = 32
+ *   z      [B * n][Z] fp32, 1 <= Z <= 32, rows b * n + k
+ *   W0 [KF + Z][K], W1, W2 [K][K], W3 [K][C], b3 [C]: fp32, TF's HWIO 1x1 filters;  s_l, t_l [K] fp32, l = 0 .. 2: the folded inference-mode
+ *   batch norm (scale, shift); s_l NULL = 1 (identity norm: t_l = the unit's bias)
+ *   a0 = relu(s0 (W0[:KF]^T feat + W0[KF:]^T z) + t0);  a_l = relu(s_l W_l^T a_{l-1} + t_l);  logits = W3^T a2 + b3;  sm = softmax(logits)
+ *   logits, sm [B * n][P][C] fp32, 2 <= C <= 8; either may be NULL, not both (PHX_E_INVAL).  Other shapes: PHX_E_SHAPE; feat must be
+ *   16-byte aligned (PHX_E_ALIGN).
+ * Rounding points.  PHX_BF16 form (v_mfma_f32_32x32x16_bf16, fp32 accumulation): W0[:KF], W1, W2 and the activations a0, a1 are rounded
+ * to bf16 (nearest even) -- where the unit-by-unit route stores them; the z term W0[KF:]^T z is an fp32 FMA chain over the fp32 filter rows
+ * and enters as an fp32 addend; scale / shift, a2, the head (fp32 FMAs over W3) and the soft-max are fp32.  PHX_F32 form: fp32 FMA chains
+ * throughout (the parity path).  Plain vector stores, no atomics: deterministic. */
+int phx_recomb_samples(const void* feat, int feat_dt, const float* z, const float* W0, const float* W1, const float* W2,
+                       const float* W3, const float* b3, const float* s0, const float* t0, const float* s1, const float* t1,
+                       const float* s2, const float* t2, float* logits, float* sm, int B, int n, int P, int KF, int K, int Z, int C,
+                       void* stream);
 
 /* ---- reparameterisation: z = mu + sigma * N(0,1) (posteriors.py:108,128; priors.py:100,120) --------- */
 /* Philox4x32-10, counter = (e/4, sample_offset + b, stream_id, *step), key = seed; see oracle/philox.py. */

@@ -522,6 +522,7 @@ class Plan(ForwardLowering, BackwardLowering):
         self._bw_skip = set()
         self._norm_head = {}          # 1x1 head op -> the conv unit whose apply pass computed it (phx_norm_apply_fused_head)
         self._pool_done = set()       # avgpool ops whose output the producer's apply pass wrote (phx_norm_apply_pool)
+        self._recomb = self._find_recomb_chains(ops)      # op -> record of a recombination chain lowered to one phx_recomb_samples launch
         fork = self._record(0) if nl > 1 else None          # lanes 1.. join the capture / wait for the memsets
         for ln in range(1, nl):
             self._lane = ln
@@ -549,7 +550,10 @@ class Plan(ForwardLowering, BackwardLowering):
                 self._wait(self.fw_event.get(self._real_producer(t)))
             n0 = len(self._cur)
             self._stamp_begin()
-            getattr(self, "_fw_" + op.type)(op, with_bw)
+            if op in self._recomb:
+                self._fw_recomb_member(op)
+            else:
+                getattr(self, "_fw_" + op.type)(op, with_bw)
             self._stamp_end("fw", op, n0)
             if nl > 1 and len(self._cur) > n0:
                 cross = any(self.op_lane.get(c, ln) != ln for o in op.outputs for c in self._real_consumers(o, opset))

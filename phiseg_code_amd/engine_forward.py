@@ -12,7 +12,7 @@ from phiseg_code_amd import runtime as rt
 from phiseg_code_amd import upconv
 from phiseg_code_amd.tfwrapper import normalisation as tfnorm
 from phiseg_code_amd.engine_common import *  # noqa: F401,F403
-from phiseg_code_amd.engine_common import _BN_SMALL, _BN_SMALL_F32, _BN_WIDE, _BN_WIDE_MAXLINES, _SKIP_HEAD_A, _DETERMINISTIC, _NREP, _NREP_MINP, _fgn_mode, _dual_enabled, _noop, _device, _TORCH_DT, _NP_DT, _ESIZE, _LIK_SIDE_MAXLVL, _WGRAD_DEFER_BLOCKS, _STAMPS  # noqa: F401
+from phiseg_code_amd.engine_common import _BN_SMALL, _BN_SMALL_F32, _BN_WIDE, _BN_WIDE_MAXLINES, _SKIP_HEAD_A, _DETERMINISTIC, _NREP, _NREP_MINP, _fgn_mode, _dual_enabled, _recomb_enabled, _noop, _device, _TORCH_DT, _NP_DT, _ESIZE, _LIK_SIDE_MAXLVL, _WGRAD_DEFER_BLOCKS, _STAMPS  # noqa: F401
 
 
 def conv_norm_route(Lb, norm, training, bw, act_dt, x_dt, y_dt, out_dt, B, H, Wd, cin_eff, cout, Gn, mfma, head1x1, concat_free, upsampled,
@@ -304,6 +304,112 @@ class ForwardLowering:
                    st.ptr(sig_op.attrs["b"]), mu.ptr, sigma.ptr, z.ptr if z is not None else None, npix, cin, zd, hw, self.rng_seed,
                    self._noise_step_ptr(), sid, self.sample_offset, self.stream)
         rec.update(npix=npix, hw=hw, sid=sid, cin=cin, zd=zd)
+
+    # ---- prob_unet2D's recombination chain at n samples per image (likelihoods.py:147-157 behind sampling_graph) as ONE launch:
+    # tile_batch(feat) -> concat with tile_pixels(z) -> three 1x1 conv units -> 1x1 head [-> soft-max aggregate] = phx_recomb_samples.
+    # Neither the tiled feature map nor the broadcast z nor any activation of the chain is materialised ---------
+    def _find_recomb_chains(self, ops):
+        """-> {member op: record} for every chain of an INFERENCE plan the kernel takes (K = 32, KF = 32 / 64, Z <= 32, 2 <= C <= 8, inference-mode
+        batch norm or identity norm, no intermediate fetched or read from outside); every other configuration keeps the unit-by-unit
+        lowering."""
+        out = {}
+        if self.loss is not None or not _recomb_enabled():
+            return out
+        opset = set(ops)
+
+        def sole_reader(t):
+            """the one op of the plan that reads t, provided nobody fetches t"""
+            cons = [c for c in t.consumers if c in opset]
+            return cons[0] if (len(cons) == 1 and t not in self.fetches and t not in self.fed) else None
+
+        def plain_1x1(op):
+            a = op.attrs
+            return (op.type == "conv_unit" and a.get("transposed") is None and a.get("general") is None and a["ksize"] == 1
+                    and op not in self._lat)
+        for tb in ops:
+            if tb.type != "tile_batch" or len(tb.inputs[0].shape) != 4:
+                continue
+            KF = tb.inputs[0].shape[-1]            # (the decoder's last level is 2 n0 wide: 64 channels into the 32-wide chain at n0 = 32)
+            if KF not in (32, 64):
+                continue
+            cat = sole_reader(tb.outputs[0])
+            if cat is None or cat.type != "concat" or cat.inputs[0] is not tb.outputs[0] or cat.inputs[1].op.type != "tile_pixels":
+                continue
+            tp = cat.inputs[1].op
+            if tp not in opset or sole_reader(tp.outputs[0]) is not cat or tp.inputs[0].kind != G.KIND_F32:
+                continue
+            Z = tp.inputs[0].shape[-1]
+            units, t = [], cat.outputs[0]
+            for _ in range(3):
+                u = sole_reader(t)
+                if u is None or not plain_1x1(u) or u.inputs[0] is not t:
+                    break
+                a = u.attrs
+                training = a["training"] if isinstance(a["training"], bool) else self.training
+                norm_ok = (a["norm"] == "batch" and not training and a["b"] is None) or (a["norm"] is None and a["b"] is not None)
+                if not norm_ok or a["act"] != "relu" or tuple(a["W"].shape[2:]) != (KF + Z if not units else 32, 32):
+                    break
+                units.append(u)
+                t = u.outputs[0]
+            if len(units) != 3:
+                continue
+            head = sole_reader(t)
+            if head is None or not plain_1x1(head) or head.inputs[0] is not t:
+                continue
+            ha = head.attrs
+            C = ha["W"].shape[-1]
+            if (ha["norm"] is not None or ha["b"] is None or ha["act"] != "identity" or head.outputs[0].kind != G.KIND_F32
+                    or ha["W"].shape[-2] != 32 or not (1 <= Z <= 32) or not (2 <= C <= 8)):
+                continue
+            members = [tb, tp, cat] + units + [head]
+            agg = sole_reader(head.outputs[0])
+            if agg is not None and agg.type == "aggregate" and agg.attrs["L"] == 1:
+                members.append(agg)            # the soft-max (and the one-level "sum") ride on the same launch
+            else:
+                agg = None
+            if len({self.op_lane[o] for o in members}) != 1:
+                continue
+            rec = dict(tb=tb, tp=tp, units=units, head=head, agg=agg, last=members[-1], KF=KF, Z=Z, C=C, n=tb.attrs["tile"])
+            for o in members:
+                out[o] = rec
+        return out
+
+    def _fw_recomb_member(self, op):
+        """A member of a fused recombination chain: its values are never made; the chain's last operator emits the launch."""
+        rec = self._recomb[op]
+        if op is not rec["last"]:
+            return
+        st, head, agg = self.store, rec["head"], rec["agg"]
+        feat, z = self.val[rec["tb"].inputs[0]], self.val[rec["tp"].inputs[0]]
+        assert isinstance(feat, Buf) and feat.dt in (F32, BF16) and z.dt == F32
+        B, P, n = feat.shape[0], feat.shape[1] * feat.shape[2], rec["n"]
+        assert z.shape[0] == B * n, "recombination chain: z has %d rows, %d images x %d samples expected" % (z.shape[0], B, n)
+        st_ptrs = []
+        for u in rec["units"]:
+            a = u.attrs
+            if a["norm"] == "batch":
+                nv = a["norm_vars"]
+                scale, shift = self._alloc((32,), F32), self._alloc((32,), F32)
+                self._bninfer_jobs.append((st.ptr(nv["gamma"]), st.ptr(nv["beta"]), st.ptr(nv["moving_mean"]), st.ptr(nv["moving_variance"]),
+                                           scale.ptr, shift.ptr, 32, tfnorm.EPS["batch"]))
+                st_ptrs += [scale.ptr, shift.ptr]
+            else:
+                st_ptrs += [None, st.ptr(a["b"])]
+        lg = sm = None
+        if agg is not None:
+            used = [t in self.fetches or any(c in self._opset for c in t.consumers) for t in agg.outputs]
+            if used[0] or not used[1]:
+                lg = self._alloc_like(agg.outputs[0])
+            if used[1]:
+                sm = self._alloc_like(agg.outputs[1])
+            self.val[agg.outputs[0]], self.val[agg.outputs[1]] = lg, sm
+            self.val[head.outputs[0]] = lg
+        else:
+            lg = self.val[head.outputs[0]] = self._alloc_like(head.outputs[0])
+        W = [st.ptr(u.attrs["W"]) for u in rec["units"]]
+        self._emit(self.L.recomb_samples, feat.ptr, feat.dt, z.ptr, W[0], W[1], W[2], st.ptr(head.attrs["W"]), st.ptr(head.attrs["b"]),
+                   *st_ptrs, lg.ptr if lg is not None else None, sm.ptr if sm is not None else None, B, n, P, rec["KF"], 32, rec["Z"], rec["C"],
+                   self.stream)
 
     def _norm_head_consumer(self, op):
         """The 1x1 head (bias, no norm, identity, fp32 out, 2 / 4 outputs) that is the ONLY reader of this unit's output, or None."""
@@ -808,6 +914,12 @@ class ForwardLowering:
         self.val[op.outputs[0]] = out
         n = op.attrs["tile"]
         assert out.shape[0] == x.shape[0] * n
+        per = x.n // x.shape[0]
+        if (per * _ESIZE[x.dt]) % 16 and x.dt == F32:
+            # rows that are no multiple of 16 bytes (prob_unet2D's mu / sigma: [B, zdim]): out[b][k][:] = x[b][:] is the pixel broadcast with
+            # n "pixels" per row
+            self._emit(self.L.broadcast_pixels_fwd, x.ptr, out.ptr, F32, x.shape[0], n, per, self.stream)
+            return
         self._emit(self.L.repeat_batch, x.ptr, out.ptr, x.shape[0], (x.n // x.shape[0]) * _ESIZE[x.dt], n, self.stream)
 
     def _fw_global_avgpool(self, op, bw):

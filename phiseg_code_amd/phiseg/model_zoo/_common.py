@@ -79,7 +79,11 @@ def hierarchical_ladder(scope_name, rng_net, inputs, teacher, zdim_0, training, 
 
 
 def probunet_encoder_head(scope_name, rng_net, inputs, zdim_0, training, scope_reuse, norm, kwargs):
+    """kwargs['tile_samples'] = n (sampling path only): the encoder -- a function of x alone -- runs once per image, mu and sigma are
+    repeated n times and z is drawn at B * n rows by the same sample() call: row b * n + k gets the noise row b * n + k of an
+    x-tiled batch gets."""
     resolution_levels = kwargs.get('resolution_levels', 7)
+    tile = int(kwargs.get('tile_samples', 1))
     widths = channel_plan(kwargs.get('n0', 32))
     g = G.get_default_graph()
     with g.variable_scope(scope_name) as scope:
@@ -88,8 +92,8 @@ def probunet_encoder_head(scope_name, rng_net, inputs, zdim_0, training, scope_r
         add_bias = norm is not tfnorm.batch_norm
         enc = encoder(inputs, 'conv_%d_%d', widths, resolution_levels, norm, training, extra=dict(add_bias=add_bias))
         mu_p = layers.conv2D(enc[-1], 'pre_mu', num_filters=zdim_0, kernel_size=(1, 1), activation=act.identity)
-        mu = [layers.global_averagepool2D(mu_p)]
+        mu = [G.tile_batch(layers.global_averagepool2D(mu_p), tile)]
         sigma_p = layers.conv2D(enc[-1], 'pre_sigma', num_filters=zdim_0, kernel_size=(1, 1), activation=act.softplus)
-        sigma = [layers.global_averagepool2D(sigma_p)]
+        sigma = [G.tile_batch(layers.global_averagepool2D(sigma_p), tile)]
         z = [sample(mu[0], sigma[0], rng_net, 0)]
     return z, mu, sigma

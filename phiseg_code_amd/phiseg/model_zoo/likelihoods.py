@@ -51,6 +51,12 @@ def prob_unet2D(z_list, training, image_size, n_classes, scope_reuse=False, norm
         if scope_reuse:
             scope.reuse_variables()
         net, cu = _unet_on_x(x, widths, resolution_levels, norm, training, norm is not tfnorm.batch_norm)
+        if z.bmul > net.bmul:
+            # n samples per image (priors.prob_unet2D with tile_samples=n): the U-Net ran once per image, its feature map is repeated
+            # for the image's samples and only the recombination layers run at batch B * n
+            if z.bmul % net.bmul:
+                raise ValueError("prob_unet2D: z has %d rows per image, the feature map %d" % (z.bmul, net.bmul))
+            net = G.tile_batch(net, z.bmul // net.bmul)
         net = G.concat([net, G.tile_pixels(z, image_size[0], image_size[1])], axis=-1)
         for t in range(3):
             net = layers.conv2D(net, 'recomb_%d' % t, num_filters=widths[0], kernel_size=(1, 1), **cu)

@@ -771,7 +771,8 @@ class phiseg():
     def sampling_graph(self, num_samples):
         """(s_out_eval, s_out_eval_sm) of a graph instance that draws `num_samples` segmentations PER fed image in one pass:
         the prior's encoder -- a function of x alone -- runs once per image, its features are repeated num_samples times
-        (graph.tile_batch) and the latent path + likelihood run at batch B * num_samples.  Same variables (scope reuse) and
+        (graph.tile_batch) and the latent path + likelihood run at batch B * num_samples.  prob_unet2D: the prior encoder AND the
+        likelihood's U-Net run once per image, mu / sigma are repeated and only the recombination layers run per sample.  Same variables (scope reuse) and
         the same Philox stream as s_out_eval_sm; output rows b * num_samples + k = sample k of image b."""
         if num_samples not in self._multi:
             cfg = self.exp_config
@@ -784,11 +785,18 @@ class phiseg():
             self._multi[num_samples] = G.aggregate_logits(s_list)
         return self._multi[num_samples]
 
+    def _one_pass_prior(self):
+        """Do predict / the Monte-Carlo map methods draw their samples through sampling_graph?  Always for the phiseg prior; for
+        prob_unet2D only with exp_config.one_pass_sampling = True (absent = False: x tiled / looped, as the reference does)."""
+        name = getattr(self.exp_config.prior, '__name__', '')
+        return name == 'phiseg' or (name == 'prob_unet2D' and bool(getattr(self.exp_config, 'one_pass_sampling', False)))
+
     def predict(self, x_in, num_samples=50, return_softmax=False):
         """phiseg_model.py:337-354: mean soft-max over num_samples prior samples, arg-max.  One pass per call when the prior
-        has an x-only encoder to share (sampling_graph); prob_unet2D draws z per image, so it keeps the reference's loop."""
+        has an x-only encoder to share (sampling_graph); prob_unet2D keeps the reference's loop unless exp_config.one_pass_sampling
+        is set (then its U-Net and prior encoder run once and only the recombination layers run per sample)."""
         fd = {self.training_pl: False, self.x_inp: x_in}
-        if num_samples > 1 and getattr(self.exp_config.prior, '__name__', '') == 'phiseg':
+        if num_samples > 1 and self._one_pass_prior():
             _, sm = self.sampling_graph(num_samples)
             sm_all = self.sess.run(sm, feed_dict=fd)                          # [B * n, X, Y, C]
             self._advance_noise()
@@ -880,8 +888,8 @@ class phiseg():
 
     # ---- Monte-Carlo uncertainty / error maps (phiseg_model.py:378-475): one sampling pass, maps formed on the device ---------------
     def _mc_maps(self, x_in, num_samples, maps, s_gt=None, amax=False):
-        """Draw num_samples segmentations per image in ONE pass (sampling_graph where the prior shares an x-only encoder, x tiled to
-        batch B * num_samples on s_out_eval otherwise: inference-mode normalisation makes the rows independent), hand the plan's
+        """Draw num_samples segmentations per image in ONE pass (sampling_graph where the prior shares an x-only encoder -- phiseg, and
+        prob_unet2D with exp_config.one_pass_sampling --, x tiled to batch B * num_samples on s_out_eval otherwise: inference-mode normalisation makes the rows independent), hand the plan's
         device buffers to phx_mc_stats on the plan's stream and copy back only the maps.  -> (dict name -> [B, X, Y], arg-max of
         the mean soft-max [B, X, Y] or None).  Advances the noise step once."""
         import torch
@@ -891,7 +899,7 @@ class phiseg():
             raise ValueError("num_samples must be 2 .. 1024 (got %d)" % n)
         x = np.asarray(x_in)
         B = x.shape[0]
-        if getattr(self.exp_config.prior, '__name__', '') == 'phiseg':
+        if self._one_pass_prior():
             lg_t, sm_t = self.sampling_graph(n)
         else:
             lg_t, sm_t = self.s_out_eval, self.s_out_eval_sm
