@@ -552,6 +552,24 @@ size_t phx_validation_metrics_ws_bytes(int I, int N, int M, int P, int C);
 int phx_validation_metrics(const float* sm, const unsigned char* gt, const unsigned char* sref, void* work, size_t work_bytes,
                            int I, int N, int M, int P, int C, int label0, float* out, void* stream);
 
+/* ---- test-set scoring from device buffers (phiseg_test_quantitative.py:39-81, phiseg_test_predictions.py:42-94; csrc/eval_metrics.hip) ----
+ * The same three scores with the same definitions, limits, status codes and `out` layout as phx_validation_metrics, read from what the
+ * sampling pass and the data provider already hold in HBM:
+ *   sm         [I * N][P][C] f32 soft-max, rows i * N + k: a sampling plan's output buffer, read in place (N >= 1; C = 2 / 4 read one
+ *              pixel's classes as one 8 / 16 byte word: PHX_E_ALIGN otherwise)
+ *   labels     [I][P][M] u8, annotator innermost (the layout DeviceBatchProvider keeps a split in), read strided
+ *   sref_annot [I] u8 DEVICE array: the annotator whose map the Dice of image i is taken against (an index >= M reads annotator M - 1);
+ *              NULL: no Dice
+ *   out        [I][2 + 8] f32: GED over labels label0 .. C-1, NCC, Dice per label; Dice slots that are not used (all of them when
+ *              sref_annot is NULL) are written as 0
+ *   work       scratch of phx_eval_metrics_ws_bytes bytes (too small: PHX_E_INVAL; a shape out of range: PHX_E_SHAPE)
+ * The pixel pass is sample-parallel (a block owns 64 pixels, its 8 waves take the samples round-robin); sum sm and sum log(sm + 1e-8)
+ * are double sums and the NCC maps are formed in double; there are no floating-point atomics -- the blocks' moment partials are added
+ * in a fixed order, so two calls on the same input give bit-identical `out`, and an image scores the same alone or in a batch. */
+size_t phx_eval_metrics_ws_bytes(int I, int N, int M, int P, int C);
+int phx_eval_metrics(const float* sm, const unsigned char* labels, const unsigned char* sref_annot, void* work, size_t work_bytes,
+                     int I, int N, int M, int P, int C, int label0, float* out, void* stream);
+
 /* ---- per-pixel Monte-Carlo sample statistics: the uncertainty / error maps of the inference API (phiseg_model.py:378-475,
  * phiseg_generate_samples.py:46-82) in one pass over the samples (csrc/mc_stats.hip) -----------------------------------------
  *   logits, sm [I][N][P][C] f32: the N samples' summed logits / their soft-max (2 <= N <= 1024, 2 <= C <= 8); either may be NULL
