@@ -680,12 +680,26 @@ int phx_dropout(const void* x, void* y, int dt, size_t per_sample, int B, float 
  * Replaces data/batch_provider.py:43-67 (next_batch), 131-137 (_select_random_label) and 140-272 (_augmentation_function with
  * the cv2 helpers of utils.py:18-38) for a data set resident in HBM: images [N][X][Y] f32, labels [N][X][Y][A] u8 (A annotators).
  * params_dev: B records of phx_augment_param_bytes() bytes in device memory,
- *   { int src, annot, flags (1 rotate | 2 crop-scale | 4 fliplr | 8 flipud), r_y, p_x, p_y; double iM[6] }
+ *   { int src, annot, flags (1 rotate | 2 crop-scale | 4 fliplr | 8 flipud | 16 elastic: phx_augment_batch_elastic only), r_y, p_x, p_y;
+ *     double iM[6] }
  * iM = inverse of cv2.getRotationMatrix2D((Y/2, X/2), angle, 1).  Output x_out [B][X][Y] f32, s_out [B][X][Y] u8 -- the plan's
  * x_input / s_input buffers can be written directly.  nlabels <= 4 (labels are interpolated as one-hot planes and arg-maxed). */
 int phx_augment_param_bytes(void);
 int phx_augment_batch(const float* images, const unsigned char* labels, const void* params_dev, float* x_out,
                       unsigned char* s_out, int B, int X, int Y, int A, int nlabels, void* stream);
+/* The same producer with the reference's fifth augmentation, the U-Net-style random elastic deformation (do_elasticaug,
+ * batch_provider.py:226-248 on utils.py:40-67 dense_image_warp / dense_image_warp_as_onehot), as a third resampling pass for the
+ * records whose flags carry bit 16 -- after rotation and crop-scale, before the flips; records without the bit give exactly what
+ * phx_augment_batch gives.  ctrl_dev [B][2][3][3] f64: the 3 x 3 control points of dx (along Y) then dy (along X), row major,
+ * already multiplied by sigma.  The displacement fields (cv2.resize INTER_CUBIC of the control points) are evaluated per pixel and
+ * never stored; the warp is cv2.remap INTER_LINEAR on 1/32-pixel fixed-point maps with BORDER_REFLECT, out(y, x) =
+ * in(y + dy, x + dx), label maps as one-hot planes in double and arg-maxed.  A restatement of OpenCV's published algorithms, not
+ * pinned against cv2 (as for the two other resamplings).  workspace: phx_augment_batch_elastic_ws_bytes bytes, 4-byte aligned
+ * (0 = none needed: the intermediates, 9 X Y bytes, fit LDS); X * Y <= 40960 as above. */
+size_t phx_augment_batch_elastic_ws_bytes(int B, int X, int Y);
+int phx_augment_batch_elastic(const float* images, const unsigned char* labels, const void* params_dev, const double* ctrl_dev,
+                              float* x_out, unsigned char* s_out, void* workspace, size_t workspace_bytes, int B, int X, int Y, int A,
+                              int nlabels, void* stream);
 
 /* ---- data-parallel gradient exchange over RCCL / xGMI ------------------------------------------------
  * The reference is single-process, single-device (phiseg_model.py:151-157); the data-parallel design shards the batch over

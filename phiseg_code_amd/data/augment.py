@@ -2,7 +2,8 @@
 _select_random_label, _augmentation_function) and data/lidc_data.py (the .train / .validation / .test surface).
 
 The data set is uploaded to HBM once (LIDC train split: ~1 GB of images + ~1 GB of 4-annotator masks -- a fraction of a
-per cent of 288 GB); a batch is then ONE kernel (phx_augment_batch: gather, random annotator, rotation, crop-scale, flips)
+per cent of 288 GB); a batch is then ONE kernel (phx_augment_batch: gather, random annotator, rotation, crop-scale, flips;
+phx_augment_batch_elastic when 'do_elasticaug' is set: the same plus the random elastic deformation of batch_provider.py:226-248)
 whose outputs can be the training plan's own input buffers -- no host round trip, where the reference spends the training
 thread on numpy / OpenCV per step (phiseg_model.py:193).
 
@@ -18,7 +19,8 @@ import numpy as np
 
 from phiseg_code_amd import philox_host
 
-ROTATE, SCALE, FLIPLR, FLIPUD = 1, 2, 4, 8
+ROTATE, SCALE, FLIPLR, FLIPUD, ELASTIC = 1, 2, 4, 8, 16
+ELASTIC_SIGMA = 10.0                                    # hard-coded in the reference (batch_provider.py:229-230), like the 3 x 3 grid
 PARAM_DTYPE = np.dtype([("src", "<i4"), ("annot", "<i4"), ("flags", "<i4"), ("r_y", "<i4"), ("p_x", "<i4"), ("p_y", "<i4"),
                         ("iM", "<f8", (6,))])
 
@@ -36,11 +38,13 @@ def rotation_inverse(cols, rows, angle_deg):
 
 
 def draw_decisions(seed, step, sample, X, Y, options, n_annot_choices):
-    """The random decisions of one sample (batch_provider.py:131-137, 197-260) from the Philox stream (seed, step, 2000 + sample)."""
+    """The random decisions of one sample (batch_provider.py:131-137, 197-260) from the Philox stream (seed, step, 2000 + sample).
+    'elastic' (do_elasticaug, batch_provider.py:226-239): None or the (dx[9], dy[9]) float64 control points np.random.normal(0, 10, 9)
+    of the two displacement fields, from a stream of their own -- every other decision is the same with the option on or off."""
     u = philox_host.uniforms(seed, step, 2000 + sample, 8)
     opt = options or {}
     nth = int(opt.get("augment_every_nth", 2))
-    d = dict(augment=int(u[0] * nth) == 0, angle=None, r_y=None, p_x=None, p_y=None, fliplr=False, flipud=False,
+    d = dict(augment=int(u[0] * nth) == 0, angle=None, r_y=None, p_x=None, p_y=None, elastic=None, fliplr=False, flipud=False,
              annot=min(int(u[7] * n_annot_choices), n_annot_choices - 1))
     if d["augment"]:
         if opt.get("do_rotations", False):
@@ -52,6 +56,9 @@ def draw_decisions(seed, step, sample, X, Y, options, n_annot_choices):
             d["r_y"] = r
             d["p_x"] = min(int(u[3] * (X - r + 1)), X - r)                       # random_integers(0, n_x - r_y)
             d["p_y"] = min(int(u[4] * (Y - r + 1)), Y - r)
+        if opt.get("do_elasticaug", False):
+            n = ELASTIC_SIGMA * philox_host.normals(seed, step, philox_host.stream_of("augment/elastic"), 18, sample=sample)
+            d["elastic"] = (n[:9].copy(), n[9:].copy())
     flipn = max(2, nth)
     if opt.get("do_fliplr", False):
         d["fliplr"] = int(u[5] * flipn) == 0
@@ -60,7 +67,9 @@ def draw_decisions(seed, step, sample, X, Y, options, n_annot_choices):
     return d
 
 
-def pack_params(decisions, src_indices, annotators, X, Y):
+def pack_params(decisions, src_indices, annotators, X, Y, ctrl=None):
+    """-> the B parameter records; ctrl (optional, [B, 2, 3, 3] float64) receives the control points of the samples that carry an
+    elastic decision (the ELASTIC flag bit is set for them either way; phx_augment_batch does not read it)."""
     rec = np.zeros(len(decisions), dtype=PARAM_DTYPE)
     for i, d in enumerate(decisions):
         flags = 0
@@ -74,6 +83,10 @@ def pack_params(decisions, src_indices, annotators, X, Y):
             flags |= FLIPLR
         if d["flipud"]:
             flags |= FLIPUD
+        if d.get("elastic") is not None:
+            flags |= ELASTIC
+            if ctrl is not None:
+                ctrl[i, 0], ctrl[i, 1] = np.reshape(d["elastic"][0], (3, 3)), np.reshape(d["elastic"][1], (3, 3))
         rec[i] = (src_indices[i], annotators[i], flags, d["r_y"] or 0, d["p_x"] or 0, d["p_y"] or 0, iM)
     return rec
 
@@ -108,7 +121,8 @@ class DeviceBatchProvider:
         self.annotator_range = list(annotator_range if annotator_range is not None else range(num_labels_per_subject))
         self.seed, self.step = int(seed), 0
         self._index_rng = np.random.default_rng([self.seed, 7])
-        self._out = {}
+        self.elastic = bool(do_augmentations and self.augmentation_options.get("do_elasticaug", False))
+        self._out, self._ws = {}, {}
 
     def _draw(self, batch_size):
         if len(self.unused_indices) < batch_size:                    # sampling without replacement across batches (51-55)
@@ -121,19 +135,23 @@ class DeviceBatchProvider:
                for j in range(batch_size)]
         if not self.do_augmentations:
             for d in dec:
-                d.update(angle=None, r_y=None, fliplr=False, flipud=False)
+                d.update(angle=None, r_y=None, elastic=None, fliplr=False, flipud=False)
         annots = [self.annotator_range[d["annot"]] for d in dec]
         self.step += 1
         self.last_decisions, self.last_indices, self.last_annotators = dec, idx, annots
-        return pack_params(dec, idx, annots, Xs, Ys)
+        ctrl = np.zeros((batch_size, 2, 3, 3), dtype=np.float64) if self.elastic else None
+        return pack_params(dec, idx, annots, Xs, Ys, ctrl), ctrl
 
     def next_batch_device(self, batch_size, x_ptr=None, s_ptr=None, stream=None):
         """One launch: the batch lands in (x_ptr, s_ptr) -- e.g. a training plan's input buffers -- or in buffers owned by the
         provider (returned as torch tensors)."""
         import torch
-        rec = self._draw(batch_size)
+        rec, ctrl = self._draw(batch_size)
         Xs, Ys = self.shape
-        par = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to(self.images_dev.device)
+        host = rec.view(np.uint8).reshape(-1)
+        if ctrl is not None:                                         # one upload: the records, then the control points (8-byte aligned)
+            host = np.concatenate([host, ctrl.view(np.uint8).reshape(-1)])
+        par = torch.from_numpy(host.copy()).to(self.images_dev.device)
         if x_ptr is None:
             key = batch_size
             if key not in self._out:
@@ -144,8 +162,17 @@ class DeviceBatchProvider:
         else:
             xo = so = None
         st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        self.L.augment_batch(self.images_dev.data_ptr(), self.labels_dev.data_ptr(), par.data_ptr(), x_ptr, s_ptr, batch_size,
-                             Xs, Ys, self.n_annot, self.nlabels, st)
+        if ctrl is None:
+            self.L.augment_batch(self.images_dev.data_ptr(), self.labels_dev.data_ptr(), par.data_ptr(), x_ptr, s_ptr, batch_size,
+                                 Xs, Ys, self.n_annot, self.nlabels, st)
+        else:
+            if batch_size not in self._ws:                           # the intermediates that do not fit LDS (e.g. 192 x 192)
+                nb = self.L.augment_batch_elastic_ws_bytes(batch_size, Xs, Ys)
+                self._ws[batch_size] = (torch.empty(nb, dtype=torch.uint8, device=par.device) if nb else None, nb)
+            ws, nb = self._ws[batch_size]
+            self.L.augment_batch_elastic(self.images_dev.data_ptr(), self.labels_dev.data_ptr(), par.data_ptr(),
+                                         par.data_ptr() + rec.nbytes, x_ptr, s_ptr, ws.data_ptr() if nb else None, nb, batch_size,
+                                         Xs, Ys, self.n_annot, self.nlabels, st)
         self._keep = par
         return xo, so
 
