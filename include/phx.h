@@ -115,6 +115,12 @@ int phx_unpad_filter_grad_accumulate(const float* dw_pad, float* dw_hwio, int Ci
 /* 1x1 convolutions run as the centre tap of a 3x3 (descriptor field k1 of phx_pack_conv3x3_bf16_multi):
  * dw_1x1[ci][co] += dw_pad[tap 4][ci][co] */
 int phx_unpad_filter_grad_center(const float* dw_pad, float* dw_1x1, int Cin, int Cin_pad, int Cout, void* stream);
+/* the folds of many layers in ONE launch (the deferred filter gradients, behind phx_wgrad_reduce_multi): jobs_dev = device array of
+ * njobs records { const float* dw_pad; float* dw; int32 Cin, Cin_pad, Cout, ntap, blk0, reserved }  (40 bytes each), ntap = 9
+ * (..._accumulate) or 1 (..._center); blk0 = first block of the job in the flat grid of 256-thread blocks (ascending, jobs[0].blk0 = 0,
+ * at least one block per job), total_blocks = end of the last job.  A job strides over its ntap * Cin * Cout elements with its blocks;
+ * every element is one add, so the result equals the per-layer launches bit for bit. */
+int phx_unpad_filter_grad_multi(const void* jobs_dev, int njobs, int total_blocks, void* stream);
 
 /* ONE launch entry for the whole family (round 6: it replaces the eleven phx_conv3x3_mfma_bf16* entry points and their *_supported
  * probes of rounds 1-5).  Prologue, epilogue and statistics mode are fields of the descriptor; a field left 0 / NULL is off.
@@ -319,6 +325,23 @@ int phx_norm_bwd_apply_fused_head(const float* dy_head, const float* w_head, int
                                   const float* shift, const float* mean, const float* rstd, const float* gamma, const float* sums2,
                                   void* dx, float* dgamma, float* dbeta, const float* fwd_sums, const float* fwd_pivot, float* dbias,
                                   int NS, int P, int C, int G, int act, int nrep, void* stream);
+/* The reduce + apply pair of a BATCH-norm layer (one statistic per channel; bf16 x, dA, dx) with a RIDER: the filter and bias gradient of
+ * a 1x1 head with nout outputs that reads the layer's activation a = act(x * scale + shift) --
+ *   dw_head[c][o] += sum_p bf16(a[p][c]) dy_head[p][o],   db_head[o] += sum_p dy_head[p][o]
+ * -- accumulated by the reduction on the x it streams anyway, instead of by a phx_head1x1_wgrad_multi job (xscale form) that reads x
+ * again.  head_acc: fp32 [nrep][C + 1][nout] (row C: the bias gradient), ZERO before the reduce launch; block b adds into replica
+ * b % nrep, block 0 of the apply launch sums the replicas and adds them into dw_head / db_head (accumulating, as dgamma / dbeta).
+ * dA == NULL: the head is the layer's only reader, dA = dy_head w_head^T is formed on the fly (phx_norm_bwd_reduce_head's arithmetic);
+ * dA != NULL: the layer has other readers, dA is their summed gradient (the head's share included) and w_head is not read.
+ * sums2 and dx equal those of the entry points without the rider.  Domain: phx_norm_head_supported(C, nout, bf16, bf16); anything else,
+ * or a null argument, is PHX_E_INVAL. */
+int phx_norm_bwd_reduce_rider(const void* dA, const float* dy_head, const float* w_head, int nout, const void* x, const float* scale,
+                              const float* shift, const float* mean, const float* rstd, float* sums2, float* head_acc, int P, int C,
+                              int act, int nrep, void* stream);
+int phx_norm_bwd_apply_fused_rider(const void* dA, const float* dy_head, const float* w_head, int nout, const void* x, const float* scale,
+                                   const float* shift, const float* mean, const float* rstd, const float* gamma, const float* sums2,
+                                   void* dx, float* dgamma, float* dbeta, const float* head_acc, float* dw_head, float* db_head, int P,
+                                   int C, int act, int nrep, void* stream);
 int phx_norm_bwd_apply_fused(const void* dA, int da_dt, const void* x, int x_dt, const float* scale, const float* shift,
                              const float* mean, const float* rstd, const float* gamma, const float* sums2, void* dx,
                              int dx_dt, float* dgamma, float* dbeta, int NS, int P, int C, int G, int act, int nrep,

@@ -154,6 +154,29 @@ __global__ void k_unpad_rows_acc(const float* __restrict__ dwp, float* __restric
         dw[i] += dwp[((size_t)t * Cpad + ci) * Cout + co];
     }
 }
+// The folds of the deferred filter gradients are leaves behind phx_wgrad_reduce_multi: ONE launch for all of them instead of
+// fifteen launches of a few thousand threads each.  jobs[j].blk0 = first block of job j in the flat grid (ascending); job j owns
+// the blocks up to jobs[j + 1].blk0 (the last job: up to the end of the grid) and strides over its elements with them.
+struct UnpadJob {
+    const float* dw_pad; float* dw;
+    int Cin, Cin_pad, Cout, ntap, blk0, reserved;
+};
+static_assert(sizeof(UnpadJob) == 40, "phx_unpad_filter_grad_multi: 40-byte job records (include/phx.h)");
+__global__ void k_unpad_rows_acc_multi(const UnpadJob* __restrict__ jobs, int njobs) {
+    int lo = 0, hi = njobs - 1;
+    while (lo < hi) {                                         // last job with blk0 <= blockIdx.x (uniform per block)
+        const int mid = (lo + hi + 1) >> 1;
+        if (jobs[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const UnpadJob j = jobs[lo];
+    const int nblk = (lo + 1 < njobs ? jobs[lo + 1].blk0 : (int)gridDim.x) - j.blk0;
+    if ((int)blockIdx.x < j.blk0 || nblk < 1) return;         // (a table that does not start at block 0 / is not ascending)
+    const int n = j.ntap * j.Cin * j.Cout;
+    for (int i = (blockIdx.x - j.blk0) * blockDim.x + threadIdx.x; i < n; i += nblk * blockDim.x) {
+        const int co = i % j.Cout, ci = (i / j.Cout) % j.Cin, t = j.ntap == 1 ? 4 : i / (j.Cout * j.Cin);
+        j.dw[i] += j.dw_pad[((size_t)t * j.Cin_pad + ci) * j.Cout + co];
+    }
+}
 
 int phx_c32_set_trace(void* dev_buf);
 int phx_wgrad_set_debug(void* trace_buf, void* blocklog_buf, int which);      // conv_wgrad.hip
@@ -886,6 +909,13 @@ int phx_unpad_filter_grad_accumulate(const float* dw_pad, float* dw_hwio, int Ci
 int phx_unpad_filter_grad_center(const float* dw_pad, float* dw_1x1, int Cin, int Cin_pad, int Cout, void* stream) {
     hipLaunchKernelGGL(k_unpad_rows_acc, dim3(phx_grid_for((size_t)Cin * Cout, 256)), dim3(256), 0,
                        (hipStream_t)stream, dw_pad, dw_1x1, Cin, Cin_pad, Cout, 1);
+    PHX_CHECK_LAUNCH();
+    return PHX_OK;
+}
+int phx_unpad_filter_grad_multi(const void* jobs_dev, int njobs, int total_blocks, void* stream) {
+    PHX_REQUIRE(jobs_dev && njobs > 0 && total_blocks >= njobs, PHX_E_INVAL, "unpad_filter_grad_multi: empty job list");
+    hipLaunchKernelGGL(k_unpad_rows_acc_multi, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream,
+                       (const UnpadJob*)jobs_dev, njobs);
     PHX_CHECK_LAUNCH();
     return PHX_OK;
 }

@@ -1280,6 +1280,19 @@ struct HeadBw {
     const float *dy, *w;
     int ph, pw, pc;      // pw > 0: x / dx are in the packed pixel order of the phase-form convolution, dA is the hi-res map [B][2 ph][2 pw][pc]
 };
+// dv = bf16(d wh^T): the head-derived upstream gradient of one pixel's V channels from the head's gradient d[HN]
+template <int V, int HN>
+__device__ __forceinline__ void da_from_head(const float (&d)[HN], const float (&hw)[V][HN], float (&dv)[V]) {
+#pragma unroll
+    for (int j = 0; j < V; j += 2) {
+        float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+        for (int o = 0; o < HN; ++o) { a0 = fmaf(d[o], hw[j][o], a0); a1 = fmaf(d[o], hw[j + 1][o], a1); }
+        const unsigned w2 = f2bf_pk(a0, a1);          // stored precision of dA (v_cvt_pk_bf16_f32: round to nearest even)
+        dv[j] = __uint_as_float(w2 << 16);
+        dv[j + 1] = __uint_as_float(w2 & 0xffff0000u);
+    }
+}
 template <typename TD, int V, int HN>
 __device__ __forceinline__ void load_da(const TD* __restrict__ dA, size_t off, const HeadBw& hb, size_t pix,
                                         const float (&hw)[V][HN > 0 ? HN : 1], float (&dv)[V]) {
@@ -1296,14 +1309,47 @@ __device__ __forceinline__ void load_da(const TD* __restrict__ dA, size_t off, c
             const float4 q = *reinterpret_cast<const float4*>(hb.dy + pix * 4);
             d[0] = q.x; d[1] = q.y; d[2] = q.z; d[3] = q.w;
         }
+        da_from_head<V, HN>(d, hw, dv);
+    }
+}
+
+// HR > 0 (rider of the backward reduction): a 1x1 head with HR outputs reads this unit's activation a = act(x * scale + shift) -- its
+// filter and bias gradient dw[c][o] = sum_p a[p][c] dy[p][o], db[o] = sum_p dy[p][o] are accumulated on the (x, scale, shift) the reduction
+// has loaded anyway (a rounded to bf16, as the stored activation and phx_head1x1_wgrad_multi's xscale form have it), instead of a
+// second pass over x by the head's own filter-gradient job.  acc[nrep][C + 1][HR]: replica blockIdx.x % nrep, row C = the bias
+// gradient; zero before the launch, folded into (dw, db) by block 0 of the apply launch (HeadFold).
+struct HeadRider {
+    const float* dy;     // [P][HR] fp32 (HN > 0: the same tensor as HeadBw::dy)
+    float* acc;
+};
+struct HeadFold {
+    const float* acc;    // NULL: nothing to fold
+    float *dw, *db;
+    int hr;
+};
+template <int HR>
+__device__ __forceinline__ void load_head_dy(const float* __restrict__ dy, size_t pix, float (&d)[HR > 0 ? HR : 1]) {
+    if constexpr (HR == 2) {
+        const float2 q = *reinterpret_cast<const float2*>(dy + pix * 2);
+        d[0] = q.x; d[1] = q.y;
+    } else if constexpr (HR == 4) {
+        const float4 q = *reinterpret_cast<const float4*>(dy + pix * 4);
+        d[0] = q.x; d[1] = q.y; d[2] = q.z; d[3] = q.w;
+    }
+}
+// acc[j][o] += bf16(act(x[j] * sc[j] + sh[j])) * d[o]
+template <int V, int HR>
+__device__ __forceinline__ void head_rider_fma(const float (&xv)[V], const float (&sc)[V], const float (&sh)[V], int act,
+                                               const float (&d)[HR > 0 ? HR : 1], float (&acc)[V][HR > 0 ? HR : 1]) {
+    static_assert(V % 2 == 0, "head rider: even vector width");
 #pragma unroll
-        for (int j = 0; j < V; j += 2) {
-            float a0 = 0.f, a1 = 0.f;
+    for (int j = 0; j < V; j += 2) {
+        const unsigned w2 = f2bf_pk(act_fwd(fmaf(xv[j], sc[j], sh[j]), act), act_fwd(fmaf(xv[j + 1], sc[j + 1], sh[j + 1]), act));
+        const float a0 = __uint_as_float(w2 << 16), a1 = __uint_as_float(w2 & 0xffff0000u);
 #pragma unroll
-            for (int o = 0; o < HN; ++o) { a0 = fmaf(d[o], hw[j][o], a0); a1 = fmaf(d[o], hw[j + 1][o], a1); }
-            const unsigned w2 = f2bf_pk(a0, a1);          // stored precision of dA (v_cvt_pk_bf16_f32: round to nearest even)
-            dv[j] = __uint_as_float(w2 << 16);
-            dv[j + 1] = __uint_as_float(w2 & 0xffff0000u);
+        for (int o = 0; o < HR; ++o) {
+            acc[j][o] = fmaf(a0, d[o], acc[j][o]);
+            acc[j + 1][o] = fmaf(a1, d[o], acc[j + 1][o]);
         }
     }
 }
@@ -1316,7 +1362,7 @@ __global__ void k_norm_bwd_apply_fused(const TD* __restrict__ dA, const TX* __re
                                        TO* __restrict__ dx, float* __restrict__ dgamma, float* __restrict__ dbeta, int P,
                                        int C, int G, int PL, int chunk, int act, int nrep,
                                        const float* __restrict__ fsums, const float* __restrict__ fpivot,
-                                       float* __restrict__ dbias, HeadBw hb) {
+                                       float* __restrict__ dbias, HeadBw hb, HeadFold hf) {
     const int CV = C / V, cg = C / G;
     const int ns = blockIdx.y;
     const int cv = threadIdx.x % CV, pl = threadIdx.x / CV;
@@ -1378,6 +1424,15 @@ __global__ void k_norm_bwd_apply_fused(const TD* __restrict__ dA, const TX* __re
             }
         }
     }
+    if (hf.acc != nullptr && blockIdx.x == 0 && blockIdx.y == 0) {
+        // the head rider of the reduction launch (HeadRider): replicas summed in order, added into the head's filter / bias gradient
+        const int nw = C * hf.hr, na = nw + hf.hr;
+        for (int i = threadIdx.x; i < na; i += blockDim.x) {
+            float a = 0.f;
+            for (int r = 0; r < nrep; ++r) a += hf.acc[(size_t)r * na + i];
+            atomicAdd(i < nw ? &hf.dw[i] : &hf.db[i - nw], a);
+        }
+    }
     __syncthreads();
     if (pl >= PL) return;
     float sc[V], sh[V], ca[V], cb[V], cc[V];
@@ -1422,11 +1477,13 @@ __global__ void k_norm_bwd_apply_fused(const TD* __restrict__ dA, const TX* __re
 }
 
 // sums2[ns][c][2] += {sum g, sum g*xhat},  g = dA * act'(x*scale+shift), xhat = (x-mean)*rstd
-template <typename TD, typename TX, int V, int HN = 0>
-__global__ __launch_bounds__(256) void k_norm_bwd_reduce(const TD* __restrict__ dA, const TX* __restrict__ x,
+// ACT >= 0 (the rider's launches): the activation is a constant of the instantiation -- no per-element dispatch on `act` in the loops
+template <typename TD, typename TX, int V, int HN = 0, int HR = 0, int ACT = -1>
+__global__ __launch_bounds__(256, HR == 2 ? 2 : 1) void k_norm_bwd_reduce(const TD* __restrict__ dA, const TX* __restrict__ x,
                                   const float* __restrict__ scale, const float* __restrict__ shift,
                                   const float* __restrict__ mean, const float* __restrict__ rstd,
-                                  float* __restrict__ sums2, int P, int C, int G, int PL, int chunk, int act, int nrep, HeadBw hb) {
+                                  float* __restrict__ sums2, int P, int C, int G, int PL, int chunk, int act, int nrep, HeadBw hb,
+                                  HeadRider hr) {
     const int CV = C / V;
     const int ns = blockIdx.y;
     const int cv = threadIdx.x % CV, pl = threadIdx.x / CV;
@@ -1442,7 +1499,17 @@ __global__ __launch_bounds__(256) void k_norm_bwd_reduce(const TD* __restrict__ 
     // one sums2 entry -- not the streaming -- set the kernel time: block b adds into replica b % nrep, the consumer
     // (k_norm_bwd_apply_fused) sums the replicas.
     sums2 += (size_t)(blockIdx.x % nrep) * gridDim.y * 2 * C;
+    const int av = ACT < 0 ? act : ACT;
     float s1[V], s2[V], sc[V], sh[V], mu[V], rs[V];
+    float racc[V][HR > 0 ? HR : 1], rb[HR > 0 ? HR : 1];      // the head rider's sums (HR > 0)
+    if constexpr (HR > 0) {
+#pragma unroll
+        for (int o = 0; o < HR; ++o) {
+            rb[o] = 0.f;
+#pragma unroll
+            for (int j = 0; j < V; ++j) racc[j][o] = 0.f;
+        }
+    }
     const int cg = C / G;
     // per-channel constants through LDS: one load per channel and block instead of one per channel and thread (red is reused
     // for the block reduction below, after the barrier that ends the streaming loop)
@@ -1464,32 +1531,48 @@ __global__ __launch_bounds__(256) void k_norm_bwd_reduce(const TD* __restrict__ 
     if (pl < PL) {
         int p = p0 + pl;
         for (; p + 3 * PL < p1; p += 4 * PL) {   // four pixels per trip, loads first (see k_norm_stats)
-            float xv[4][V], dv[4][V];
+            float xv[4][V], dv[4][V], hd[4][HR > 0 ? HR : 1];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const size_t off = ((size_t)ns * P + p + u * PL) * C + (size_t)cv * V;
                 VecIO<TX, V>::load(x, off, xv[u]);
-                load_da<TD, V, HN>(dA, off, hb, (size_t)ns * P + p + u * PL, hw, dv[u]);
+                if constexpr (HR > 0) load_head_dy<HR>(hr.dy, (size_t)ns * P + p + u * PL, hd[u]);
+                if constexpr (HR > 0 && HN > 0) da_from_head<V, HN>(hd[u], hw, dv[u]);      // (the same head: one load of its gradient)
+                else load_da<TD, V, HN>(dA, off, hb, (size_t)ns * P + p + u * PL, hw, dv[u]);
             }
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
+            for (int u = 0; u < 4; ++u) {
 #pragma unroll
                 for (int j = 0; j < V; ++j) {
-                    const float g = dv[u][j] * act_grad_pre(xv[u][j] * sc[j] + sh[j], act);
+                    const float g = dv[u][j] * act_grad_pre(xv[u][j] * sc[j] + sh[j], av);
                     s1[j] += g;
                     s2[j] += g * (xv[u][j] - mu[j]) * rs[j];
                 }
+                if constexpr (HR > 0) {
+                    head_rider_fma<V, HR>(xv[u], sc, sh, av, hd[u], racc);
+#pragma unroll
+                    for (int o = 0; o < HR; ++o) rb[o] += hd[u][o];
+                }
+            }
         }
         for (; p < p1; p += PL) {
             float xv[V], dv[V];
             const size_t off = ((size_t)ns * P + p) * C + (size_t)cv * V;
             VecIO<TX, V>::load(x, off, xv);
-            load_da<TD, V, HN>(dA, off, hb, (size_t)ns * P + p, hw, dv);
+            float hd[HR > 0 ? HR : 1];
+            if constexpr (HR > 0) load_head_dy<HR>(hr.dy, (size_t)ns * P + p, hd);
+            if constexpr (HR > 0 && HN > 0) da_from_head<V, HN>(hd, hw, dv);
+            else load_da<TD, V, HN>(dA, off, hb, (size_t)ns * P + p, hw, dv);
 #pragma unroll
             for (int j = 0; j < V; ++j) {
-                const float g = dv[j] * act_grad_pre(xv[j] * sc[j] + sh[j], act);
+                const float g = dv[j] * act_grad_pre(xv[j] * sc[j] + sh[j], av);
                 s1[j] += g;
                 s2[j] += g * (xv[j] - mu[j]) * rs[j];
+            }
+            if constexpr (HR > 0) {
+                head_rider_fma<V, HR>(xv, sc, sh, av, hd, racc);
+#pragma unroll
+                for (int o = 0; o < HR; ++o) rb[o] += hd[o];
             }
         }
 #pragma unroll
@@ -1503,6 +1586,38 @@ __global__ __launch_bounds__(256) void k_norm_bwd_reduce(const TD* __restrict__ 
         float a = 0.f;
         for (int q = 0; q < PL; ++q) a += red[q * 2 * C + i];
         atomicAdd(&sums2[(size_t)ns * 2 * C + i], a);
+    }
+    if constexpr (HR > 0) {
+        // the rider's sums through the same LDS rows, two head outputs per round: red[pl][c][2]
+        float* hacc = hr.acc + (size_t)(blockIdx.x % nrep) * (C + 1) * HR;
+#pragma unroll
+        for (int o0 = 0; o0 < HR; o0 += 2) {
+            __syncthreads();
+            if (pl < PL) {
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    red[(pl * C + cv * V + j) * 2 + 0] = racc[j][o0];
+                    red[(pl * C + cv * V + j) * 2 + 1] = racc[j][o0 + 1];
+                }
+            }
+            __syncthreads();
+            for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {
+                float a = 0.f;
+                for (int q = 0; q < PL; ++q) a += red[q * 2 * C + i];
+                atomicAdd(&hacc[(i >> 1) * HR + o0 + (i & 1)], a);
+            }
+        }
+        __syncthreads();
+        if (cv == 0 && pl < PL) {
+#pragma unroll
+            for (int o = 0; o < HR; ++o) red[pl * HR + o] = rb[o];
+        }
+        __syncthreads();
+        if (threadIdx.x < HR) {
+            float a = 0.f;
+            for (int q = 0; q < PL; ++q) a += red[q * HR + threadIdx.x];
+            atomicAdd(&hacc[C * HR + threadIdx.x], a);
+        }
     }
 }
 
@@ -2281,7 +2396,8 @@ static int norm_bwd_apply_impl(const void* dA, int da_dt, const void* x, int x_d
         PHX_REQUIRE(stream_geometry(P, C, V, &PL, &threads, &chunk, &nchunks, NS) == 0, PHX_E_SHAPE, "norm_bwd_apply_fused: C too large");
         hipLaunchKernelGGL((k_norm_bwd_apply_fused<TD, TX, TD, V>), dim3(nchunks, NS), dim3(threads),
                            (size_t)(7 * C + 2 * G) * sizeof(float), (hipStream_t)stream, (const TD*)dA, (const TX*)x, scale, shift, mean, rstd, gamma, sums2,
-                           (TD*)dx, dgamma, dbeta, P, C, G, PL, chunk, act, nrep, fwd_sums, fwd_pivot, dbias, HeadBw{nullptr, nullptr, ph, pw, C});
+                           (TD*)dx, dgamma, dbeta, P, C, G, PL, chunk, act, nrep, fwd_sums, fwd_pivot, dbias, HeadBw{nullptr, nullptr, ph, pw, C},
+                           HeadFold{nullptr, nullptr, nullptr, 0});
     })));
     PHX_CHECK_LAUNCH();
     return PHX_OK;
@@ -2302,7 +2418,7 @@ int phx_norm_bwd_reduce_head(const float* dy_head, const float* w_head, int nout
 #define NRH_LAUNCH(HNv)                                                                                                           \
     hipLaunchKernelGGL((k_norm_bwd_reduce<bf16_t, bf16_t, 8, HNv>), dim3(nchunks, NS), dim3(threads),                              \
                        (size_t)(PL > 2 ? PL : 2) * C * 2 * sizeof(float), (hipStream_t)stream, (const bf16_t*)nullptr, (const bf16_t*)x, \
-                       scale, shift, mean, rstd, sums2, P, C, G, PL, chunk, act, nrep, HeadBw{dy_head, w_head})
+                       scale, shift, mean, rstd, sums2, P, C, G, PL, chunk, act, nrep, HeadBw{dy_head, w_head}, HeadRider{nullptr, nullptr})
     if (nout == 2) NRH_LAUNCH(2); else NRH_LAUNCH(4);
 #undef NRH_LAUNCH
     PHX_CHECK_LAUNCH();
@@ -2320,9 +2436,69 @@ int phx_norm_bwd_apply_fused_head(const float* dy_head, const float* w_head, int
     hipLaunchKernelGGL((k_norm_bwd_apply_fused<bf16_t, bf16_t, bf16_t, 8, HNv>), dim3(nchunks, NS), dim3(threads),                 \
                        (size_t)(7 * C + 2 * G) * sizeof(float), (hipStream_t)stream, (const bf16_t*)nullptr, (const bf16_t*)x, scale, shift, \
                        mean, rstd, gamma, sums2, (bf16_t*)dx, dgamma, dbeta, P, C, G, PL, chunk, act, nrep, fwd_sums, fwd_pivot, dbias, \
-                       HeadBw{dy_head, w_head})
+                       HeadBw{dy_head, w_head}, HeadFold{nullptr, nullptr, nullptr, 0})
     if (nout == 2) NAH_LAUNCH(2); else NAH_LAUNCH(4);
 #undef NAH_LAUNCH
+    PHX_CHECK_LAUNCH();
+    return PHX_OK;
+}
+
+/* The reduce + apply pair of a BATCH-norm layer (one statistic per channel, bf16 tensors) with the filter / bias gradient of a 1x1 head
+ * that reads the layer's activation riding on it (HeadRider / HeadFold above): phx_norm_head_supported's domain, everything else is
+ * PHX_E_INVAL.  dA == NULL: the head is the layer's only reader and dA = dy_head w_head^T is formed on the fly (the _head entry points'
+ * arithmetic); else dA is the tensor and w_head is not read. */
+static int norm_rider_check(const void* x, const float* dy_head, const float* w_head, const void* dA, int nout, const float* hacc, int P,
+                            int C, int nrep, const char* who) {
+    PHX_REQUIRE(x && dy_head && hacc && (dA || w_head) && P >= 1 && nrep >= 1, PHX_E_INVAL, who);
+    PHX_REQUIRE(C >= 8 && phx_norm_head_supported(C, nout, PHX_BF16, PHX_BF16), PHX_E_INVAL, who);
+    return PHX_OK;
+}
+int phx_norm_bwd_reduce_rider(const void* dA, const float* dy_head, const float* w_head, int nout, const void* x, const float* scale,
+                              const float* shift, const float* mean, const float* rstd, float* sums2, float* head_acc, int P, int C,
+                              int act, int nrep, void* stream) {
+    if (int rc = norm_rider_check(x, dy_head, w_head, dA, nout, head_acc, P, C, nrep,
+                                  "norm_bwd_reduce_rider: bf16, C / 8 a power of two <= 64, nout in {2, 4}, non-null arguments")) return rc;
+    int PL, threads, chunk, nchunks;
+    PHX_REQUIRE(norm_geometry(P, C, 8, &PL, &threads, &chunk, &nchunks, 1, nrep) == 0, PHX_E_INVAL, "norm_bwd_reduce_rider: C too large");
+    if (phx_deterministic() && nchunks > nrep) {               // (as phx_norm_bwd_reduce: block b owns replica b)
+        chunk = (P + nrep - 1) / nrep;
+        nchunks = (P + chunk - 1) / chunk;
+    }
+#define NRR_LAUNCH_A(HNv, HRv, ACTv)                                                                                             \
+    hipLaunchKernelGGL((k_norm_bwd_reduce<bf16_t, bf16_t, 8, HNv, HRv, ACTv>), dim3(nchunks, 1), dim3(threads),                    \
+                       (size_t)(PL > 2 ? PL : 2) * C * 2 * sizeof(float), (hipStream_t)stream, (const bf16_t*)dA, (const bf16_t*)x, \
+                       scale, shift, mean, rstd, sums2, P, C, C, PL, chunk, act, nrep, HeadBw{dy_head, w_head, 0, 0, C},           \
+                       HeadRider{dy_head, head_acc})
+#define NRR_LAUNCH(HNv, HRv)                                                                                                      \
+    do {                                                                                                                          \
+        if (act == PHX_ACT_RELU) NRR_LAUNCH_A(HNv, HRv, PHX_ACT_RELU);                                                            \
+        else if (act == PHX_ACT_ID) NRR_LAUNCH_A(HNv, HRv, PHX_ACT_ID);                                                           \
+        else NRR_LAUNCH_A(HNv, HRv, -1);                                                                                          \
+    } while (0)
+    if (dA == nullptr) { if (nout == 2) NRR_LAUNCH(2, 2); else NRR_LAUNCH(4, 4); }
+    // (dA a tensor: the specialised copies need more registers than two waves per SIMD leave -- the run-time dispatch stays)
+    else { if (nout == 2) NRR_LAUNCH_A(0, 2, -1); else NRR_LAUNCH_A(0, 4, -1); }
+#undef NRR_LAUNCH
+#undef NRR_LAUNCH_A
+    PHX_CHECK_LAUNCH();
+    return PHX_OK;
+}
+int phx_norm_bwd_apply_fused_rider(const void* dA, const float* dy_head, const float* w_head, int nout, const void* x, const float* scale,
+                                   const float* shift, const float* mean, const float* rstd, const float* gamma, const float* sums2,
+                                   void* dx, float* dgamma, float* dbeta, const float* head_acc, float* dw_head, float* db_head, int P,
+                                   int C, int act, int nrep, void* stream) {
+    if (int rc = norm_rider_check(x, dy_head, w_head, dA, nout, head_acc, P, C, nrep,
+                                  "norm_bwd_apply_fused_rider: bf16, C / 8 a power of two <= 64, nout in {2, 4}, non-null arguments")) return rc;
+    PHX_REQUIRE(dx && dw_head && db_head, PHX_E_INVAL, "norm_bwd_apply_fused_rider: null output");
+    int PL, threads, chunk, nchunks;
+    PHX_REQUIRE(stream_geometry(P, C, 8, &PL, &threads, &chunk, &nchunks, 1) == 0, PHX_E_INVAL, "norm_bwd_apply_fused_rider: C too large");
+#define NAR_LAUNCH(HNv)                                                                                                           \
+    hipLaunchKernelGGL((k_norm_bwd_apply_fused<bf16_t, bf16_t, bf16_t, 8, HNv>), dim3(nchunks, 1), dim3(threads),                  \
+                       (size_t)(7 * C + 2 * C) * sizeof(float), (hipStream_t)stream, (const bf16_t*)dA, (const bf16_t*)x, scale, shift, \
+                       mean, rstd, gamma, sums2, (bf16_t*)dx, dgamma, dbeta, P, C, C, PL, chunk, act, nrep, (const float*)nullptr,  \
+                       (const float*)nullptr, (float*)nullptr, HeadBw{dy_head, w_head, 0, 0, C}, HeadFold{head_acc, dw_head, db_head, nout})
+    if (dA != nullptr) NAR_LAUNCH(0); else if (nout == 2) NAR_LAUNCH(2); else NAR_LAUNCH(4);
+#undef NAR_LAUNCH
     PHX_CHECK_LAUNCH();
     return PHX_OK;
 }
@@ -2355,7 +2531,7 @@ static int norm_bwd_reduce_impl(const void* dA, int da_dt, const void* x, int x_
         }
         hipLaunchKernelGGL((k_norm_bwd_reduce<TD, TX, V>), dim3(nchunks, NS), dim3(threads),
                            (size_t)(PL > 2 ? PL : 2) * C * 2 * sizeof(float), (hipStream_t)stream, (const TD*)dA, (const TX*)x, scale,
-                           shift, mean, rstd, sums2, P, C, G, PL, chunk, act, nrep, HeadBw{nullptr, nullptr, ph, pw, C});
+                           shift, mean, rstd, sums2, P, C, G, PL, chunk, act, nrep, HeadBw{nullptr, nullptr, ph, pw, C}, HeadRider{nullptr, nullptr});
     })));
     PHX_CHECK_LAUNCH();
     return PHX_OK;

@@ -249,6 +249,7 @@ class Plan(ForwardLowering, BackwardLowering):
         self._wpk = {}
         self._tail_jobs = []          # launches that follow the deferred ones on lane 0 (padded-filter folds)
         self._wgm_jobs = {}           # deferred small-map filter gradients by kernel variant: records, total blocks, LDS bytes
+        self._head_riders = {}        # conv unit -> the 1x1 head whose filter gradient rides on its norm backward (_head_rider_for)
         self._headw_jobs = {}         # deferred 1x1-head filter gradients by (x dtype, nout): (x, dy, dw, db, npix, C, PL, chunk, grid, lds)
         self._wgr_jobs = []           # deferred filter-gradient reductions: (ws, dw, nslice, Cin, Cout, tci, tco, gx, gy)
         self._pack_jobs = []          # (w, wpk_fwd, wpk_dgrad, Cin, Cin_pad, Cout): ONE multi-filter pack launch per run
@@ -334,8 +335,19 @@ class Plan(ForwardLowering, BackwardLowering):
             desc = torch.from_numpy(rec.view(np.uint8).copy()).to(_device())
             self._keep.append(desc)
             self._emit(self.L.wgrad_reduce_multi, desc.data_ptr(), len(self._wgr_jobs), blk, self.stream)
-        for fn, args in self._tail_jobs:
-            self._emit(fn, *args, self.stream)
+        if self._tail_jobs:
+            rec = np.zeros(len(self._tail_jobs), dtype=[("dw_pad", "<u8"), ("dw", "<u8"), ("cin", "<i4"), ("cin_pad", "<i4"), ("cout", "<i4"),
+                                                        ("ntap", "<i4"), ("blk0", "<i4"), ("reserved", "<i4")])
+            blk = 0
+            for i, j in enumerate(self._tail_jobs):
+                rec[i] = tuple(j) + (blk, 0)
+                blk += (j[5] * j[2] * j[4] + 255) // 256          # one element per thread, as the per-layer launches
+            desc = torch.from_numpy(rec.view(np.uint8).copy()).to(_device())
+            self._keep.append(desc)
+            self._emit(self.L.unpad_filter_grad_multi, desc.data_ptr(), len(self._tail_jobs), blk, self.stream)
+        for r in self._head_riders.values():          # (a producer whose backward never reached the reduce + apply pair)
+            self._headw_jobs.setdefault(r["key"], []).append(r["job"])
+        self._head_riders = {}
         for (xdt, nout), jobs in self._headw_jobs.items():
             rec = np.zeros(len(jobs), dtype=[("x", "<u8"), ("dy", "<u8"), ("dw", "<u8"), ("db", "<u8"), ("npix", "<u8"), ("C", "<i4"),
                                              ("PL", "<i4"), ("chunk", "<i4"), ("blk0", "<i4"), ("xscale", "<u8"), ("xshift", "<u8"),

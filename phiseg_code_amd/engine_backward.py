@@ -8,7 +8,7 @@ import numpy as np
 from phiseg_code_amd import runtime as rt
 from phiseg_code_amd import upconv
 from phiseg_code_amd.engine_common import *  # noqa: F401,F403
-from phiseg_code_amd.engine_common import _BN_SMALL, _BN_SMALL_F32, _BN_WIDE, _BN_WIDE_MAXLINES, _DETERMINISTIC, _NREP, _NREP_MINP, _fgn_mode, _dual_enabled, _noop, _device, _TORCH_DT, _NP_DT, _ESIZE, _LIK_SIDE_MAXLVL, _WGRAD_DEFER_BLOCKS, _STAMPS  # noqa: F401
+from phiseg_code_amd.engine_common import _HEAD_RIDER_NOUT, _BN_SMALL, _BN_SMALL_F32, _BN_WIDE, _BN_WIDE_MAXLINES, _DETERMINISTIC, _NREP, _NREP_MINP, _fgn_mode, _dual_enabled, _noop, _device, _TORCH_DT, _NP_DT, _ESIZE, _LIK_SIDE_MAXLVL, _WGRAD_DEFER_BLOCKS, _STAMPS  # noqa: F401
 
 
 class BackwardLowering:
@@ -217,12 +217,27 @@ class BackwardLowering:
             else:
                 self._add_grad(t, write_fn=lambda g: self._emit(self.L.memcpy_d2d, g.ptr, d.ptr, d.nbytes, self.stream))
 
-    def _norm_bwd(self, sv, nv, dA, dY, C, act, nrep, sums2, bias=None, tagged=False, s2d=()):
+    def _norm_bwd(self, sv, nv, dA, dY, C, act, nrep, sums2, bias=None, tagged=False, s2d=(), rider=None):
         """Generic normalisation backward: the reduction over (dA, y), then the fused apply that writes dY and adds dgamma / dbeta.
         bias: (forward sums, forward pivot, db) pointers of the closed-form conv-bias gradient (phx_norm_bwd_apply_fused_bias and the
         _s2d / _head forms), None without.  s2d: (h, w) of a phase-form unit, whose hi-res dA is read through the space-to-depth
-        permutation.  A HeadGrad dA is formed on the fly (dy_head w_head^T)."""
+        permutation.  A HeadGrad dA is formed on the fly (dy_head w_head^T).  rider: the filter / bias gradient of that head
+        (_head_rider_for) rides on the pair; where the pair cannot carry it, its job goes back to the heads' own launch."""
         Lb, y = self.L, sv.y
+        if rider is not None:
+            ok = (isinstance(dA, HeadGrad) and dA.dy.ptr == rider["dy"] and dA.nout == rider["nout"] and not s2d
+                  and (bias is None or bias[2] is None) and sv.NS == 1 and sv.G == C and y.dt == BF16 and dY.dt == BF16)
+            if not ok:
+                self._headw_jobs.setdefault(rider["key"], []).append(rider["job"])
+            else:
+                hacc = self._alloc_zeroed(nrep * (C + 1) * rider["nout"])
+                lead = (None, rider["dy"], dA.w_ptr, rider["nout"], y.ptr, sv.scale.ptr, sv.shift.ptr, sv.mean.ptr, sv.rstd.ptr)
+                self._emit(Lb.norm_bwd_reduce_rider, *lead, sums2.ptr, hacc.ptr, sv.P, C, act, nrep, self.stream,
+                           tag="bytes_norm_bwd_reduce" if tagged else None, flops=float(y.nbytes))
+                self._emit(Lb.norm_bwd_apply_fused_rider, *lead, self.store.ptr(nv["gamma"]), sums2.ptr, dY.ptr, self.store.grad_ptr(nv["gamma"]),
+                           self.store.grad_ptr(nv["beta"]), hacc.ptr, rider["dw"], rider["db"], sv.P, C, act, nrep, self.stream,
+                           tag="bytes_norm_bwd_apply" if tagged else None, flops=float(y.nbytes + dY.nbytes))
+                return
         if isinstance(dA, HeadGrad):
             lead, nb, ydt = (dA.dy.ptr, dA.w_ptr, dA.nout, y.ptr), 0, ()
             reduce, apply = Lb.norm_bwd_reduce_head, Lb.norm_bwd_apply_fused_head
@@ -378,7 +393,7 @@ class BackwardLowering:
                        tag="bytes_norm_bwd_onepass", flops=float(dA.nbytes + y.nbytes + dY.nbytes))
         else:
             s2d = (sv.x.shape[1] // 2, sv.x.shape[2] // 2) if sv.upconv is not None else ()
-            self._norm_bwd(sv, nv, dA, dY, cout, act, nrep, sums2, bias=bias, tagged=True, s2d=s2d)
+            self._norm_bwd(sv, nv, dA, dY, cout, act, nrep, sums2, bias=bias, tagged=True, s2d=s2d, rider=self._head_riders.pop(op, None))
         return dY, fs is not None
 
     # ---- the units off the common path: stages 2 and 3 in one method each ------------------------------------------------------
@@ -428,7 +443,14 @@ class BackwardLowering:
             au = self.saved[prod].a_unwritten if prod is not None else None
             src, extra = (x, ()) if au is None else (au["y"], ((au["scale"].ptr, au["shift"].ptr, au["act"]),))
             # (au: the producer never wrote a = act(bn(y)) -- the job re-forms it from y: phx_head1x1_wgrad_multi, xscale)
-            self._headw_jobs.setdefault((src.dt, cout), []).append((src.ptr, dY.ptr, dw, db, B * H * Wd, cin, *plan4) + extra)
+            key, job = (src.dt, cout), (src.ptr, dY.ptr, dw, db, B * H * Wd, cin, *plan4) + extra
+            rprod = self._head_rider_for(op, B * H * Wd, cin, cout)
+            if rprod is not None:
+                # the producer's norm backward (later in the backward order, same lane) streams the very tensor this job would read
+                # again: the head's filter / bias gradient rides on its reduction (phx_norm_bwd_reduce_rider)
+                self._head_riders[rprod] = dict(dy=dY.ptr, dw=dw, db=db, nout=cout, key=key, job=job)
+            else:
+                self._headw_jobs.setdefault(key, []).append(job)
         elif sv.head1x1:
             self._emit(Lb.head1x1_wgrad, x.ptr, x.dt, dY.ptr, dw, db, B * H * Wd, cin, cout, S)
         elif sv.padded or sv.mfma:
@@ -450,6 +472,23 @@ class BackwardLowering:
                        B, H, Wd, cin, cout, k, S)
         else:
             self._emit(Lb.conv2d_direct_wgrad, x.ptr, x.dt, dY.ptr, dY.dt, dw, db, B, H, Wd, cin, cout, k, S)
+
+    def _head_rider_for(self, op, npix, cin, nout):
+        """The conv unit whose norm backward carries the filter gradient of 1x1 head `op` as a rider, or None: the batch-norm unit on
+        the head's lane whose ONLY reader the head is (its gradient is the HeadGrad placeholder, so its backward is the reduce + apply
+        pair of _norm_bwd -- never the one-launch forms or the phase form), in the kernels' domain (phx_norm_head_supported).  The
+        form for a unit with further readers (dA a tensor) is in the library but lost to the stand-alone job where it was measured
+        (LABBOOK), so such heads keep their job.  Deterministic mode keeps the heads' own launch."""
+        if not _head_rider_enabled() or _DETERMINISTIC or self.act_dt != BF16 or nout not in _HEAD_RIDER_NOUT:
+            return None
+        prod = self._norm_head.get(op)
+        psv = self.saved.get(prod) if prod is not None else None
+        if (not isinstance(psv, ConvSaved) or prod.outputs[0] is not op.inputs[0] or self.op_lane.get(prod) != self.op_lane.get(op)
+                or psv.route is not NormRoute.GENERIC or psv.norm != "batch" or psv.upconv is not None or prod.attrs["b"] is not None
+                or psv.y is None or psv.y.dt != BF16 or psv.NS != 1 or psv.P != npix or psv.y.shape[3] != cin or psv.G != cin
+                or prod in self._head_riders or not self.L.norm_head_supported(cin, nout, BF16, BF16)):
+            return None
+        return prod
 
     def _bw_filter_mfma(self, op, sv, dY, dw, db):
         """bf16 MFMA filter gradient.  Padded layers (zero-padded input channels / 1x1 as centre tap): the gradient goes to a padded
@@ -495,11 +534,11 @@ class BackwardLowering:
         else:
             self._emit(Lb.conv3x3_wgrad_mfma_bf16, *wargs, S, **tag)
         if sv.padded:
-            unpad = (Lb.unpad_filter_grad_center if sv.k1 else Lb.unpad_filter_grad_accumulate, (tgt, dw, cin, ce, cout))
             if deferred:
-                self._tail_jobs.append(unpad)             # after the deferred launches, on lane 0
+                # after the deferred launches, on lane 0: ONE launch folds them all (phx_unpad_filter_grad_multi)
+                self._tail_jobs.append((tgt, dw, cin, ce, cout, 1 if sv.k1 else 9))
             else:
-                self._emit(unpad[0], *unpad[1], S)
+                self._emit(Lb.unpad_filter_grad_center if sv.k1 else Lb.unpad_filter_grad_accumulate, tgt, dw, cin, ce, cout, S)
         if db is not None:
             self._emit(Lb.channel_sum_accumulate, dY.ptr, dY.dt, db, B * H * Wd, cout, S)
 

@@ -11,7 +11,7 @@ from phiseg_code_amd import graph as G
 from phiseg_code_amd import runtime as rt
 from phiseg_code_amd.tfwrapper import normalisation as tfnorm
 
-__all__ = ['F32', 'BF16', 'U8', '_TORCH_DT', '_NP_DT', '_ESIZE', '_LIK_SIDE_MAXLVL', '_WGRAD_DEFER_BLOCKS', '_NREP', '_NREP_MINP', '_STAMPS', '_DETERMINISTIC', '_BN_SMALL', '_BN_SMALL_F32', '_BN_WIDE', '_BN_WIDE_MAXLINES', '_SKIP_HEAD_A', '_POOL_FUSE', '_xf_enabled', '_upconv_min_h', 'UpBuf', '_fgn_mode', '_dual_enabled', '_f32_mfma_enabled', '_recomb_enabled', '_onepass_enabled', '_noop', '_device', 'live_variables', 'device_sync', 'Buf', 'DualBuf', 'HeadGrad', 'SliceGrad', 'XfBuf', 'NormRoute', 'StatsSource', 'ConvSaved']
+__all__ = ['F32', 'BF16', 'U8', '_TORCH_DT', '_NP_DT', '_ESIZE', '_LIK_SIDE_MAXLVL', '_WGRAD_DEFER_BLOCKS', '_NREP', '_NREP_MINP', '_STAMPS', '_DETERMINISTIC', '_BN_SMALL', '_BN_SMALL_F32', '_BN_WIDE', '_BN_WIDE_MAXLINES', '_SKIP_HEAD_A', '_POOL_FUSE', '_xf_enabled', '_upconv_min_h', 'UpBuf', '_fgn_mode', '_dual_enabled', '_f32_mfma_enabled', '_recomb_enabled', '_onepass_enabled', '_head_rider_enabled', '_HEAD_RIDER_NOUT', '_noop', '_device', 'live_variables', 'device_sync', 'Buf', 'DualBuf', 'HeadGrad', 'SliceGrad', 'XfBuf', 'NormRoute', 'StatsSource', 'ConvSaved']
 
 F32, BF16, U8 = rt.F32, rt.BF16, 2
 _TORCH_DT = {F32: torch.float32, BF16: torch.bfloat16, U8: torch.uint8}
@@ -75,6 +75,17 @@ def _onepass_enabled():
     # batch-norm backward of the mid-size layers in ONE launch (phx_bn_bwd_onepass: (dA, y) held in registers across a grid barrier)
     # instead of phx_norm_bwd_reduce + phx_norm_bwd_apply_fused.  A/B hook, read when a plan is built.
     return os.environ.get("PHX_ONEPASS", "1") == "1"
+
+
+# head widths whose rider was measured faster than the stand-alone job it replaces (LABBOOK, tools/bench_norm_head.py)
+_HEAD_RIDER_NOUT = (2, 4)
+
+
+def _head_rider_enabled():
+    # the filter / bias gradient of a 1x1 head as a rider of its producer's batch-norm backward reduction (phx_norm_bwd_reduce_rider +
+    # phx_norm_bwd_apply_fused_rider) instead of a job of phx_head1x1_wgrad_multi that reads the producer's tensor again.  A/B hook,
+    # read when a plan is built.
+    return os.environ.get("PHX_HEAD_RIDER", "1") != "0"
 
 
 def _noop():
