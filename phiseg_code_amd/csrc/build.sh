@@ -3,12 +3,12 @@
 set -e
 cd "$(dirname "$0")"
 OUT=../libphx.so
-SRCS="runtime.hip elementwise.hip losses_opt.hip conv_direct.hip conv_f32_mfma.hip conv_mfma.hip conv_wgrad.hip conv_pp.hip conv_c32.hip heads.hip metrics.hip eval_metrics.hip mc_stats.hip comm.hip augment.hip tconv.hip gconv.hip upconv.hip summary.hip recomb.hip"
+SRCS=$(cat SOURCES)                # one translation unit per line; tools/build_variant.sh reads the same list
 OBJS=""
 DOBJS=""
 for s in $SRCS; do
   o="build_${s%.hip}.o"
-  if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ phx_common.h -nt "$o" ] || [ conv_common.h -nt "$o" ] || [ philox.h -nt "$o" ] || [ ../../include/phx.h -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ phx_common.h -nt "$o" ] || [ conv_common.h -nt "$o" ] || [ philox.h -nt "$o" ] || [ vec_io.h -nt "$o" ] || [ norm_common.h -nt "$o" ] || [ ../../include/phx.h -nt "$o" ]; then
     rm -f "$o"                       # (a failed compile must not leave the previous object behind for the link)
     # conv_pp.hip: no SLP vectorisation -- packed fp32 VALU (v_pk_fma_f32 / v_pk_add_f32 formed from adjacent scalar operations) costs
     # issue slots beside the partner wave's MFMA stream, and a v_pk_fma_f32 issued straight behind a buffer_store_dwordx4 whose data

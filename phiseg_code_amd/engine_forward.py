@@ -621,7 +621,7 @@ class ForwardLowering:
                    self.stream, tag="bytes_norm_apply", flops=float(y.nbytes + out.nbytes))
 
     def _fw_unit_bn_small(self, o, sv):
-        # H <= 8 levels: the whole batch-norm layer in one launch (phx_bn_small_fwd / _bwd; csrc/elementwise.hip)
+        # H <= 8 levels: the whole batch-norm layer in one launch (phx_bn_small_fwd / _bwd; csrc/norm_onelaunch.hip)
         # (policy P <= 1024, the H <= 4 levels: at P = 4096 the single launch measured no faster than the chain)
         if sv.route is NormRoute.BN_SMALL_F32Y:
             self._conv_f32out(o, 1)
