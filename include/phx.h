@@ -562,6 +562,51 @@ int phx_weighted_sum(const float* const* ptrs, const float* weights, int n, floa
 int phx_l2_masked(const float* p, const float* mask, size_t n, float scale, float* work256, float* out, void* stream);
 int phx_axpy_masked(float* g, const float* p, const float* mask, size_t n, float alpha, void* stream);
 
+/* ---- segmentation losses (tfwrapper/losses.py:8-159; csrc/seg_losses.hip) ------------------------------------------------------
+ * logits [B,H,W,C] fp32 with 2 <= C <= 8 (anything else: PHX_E_INVAL, nothing is launched; logit heads are fp32 in bf16 plans too, so
+ * there is no bf16 form), labels [B,H,W] u8 class indices -- the one-hot of the reference is folded into the read (a label >= C is an
+ * all-zero row).  A pixel's classes are read as one 8- / 16-byte word where C is even / a multiple of 4 (PHX_E_ALIGN otherwise).
+ * No floating-point atomics: every block leaves one partial record, a finishing launch adds the records in block order (in double), so
+ * two calls on the same input give the same bits whether or not PHX_DETERMINISTIC is set.  A too-small workspace is PHX_E_INVAL.
+ *
+ * get_dice / dice_loss in three launches:
+ *   phx_dice_sums    one pass over the pixels -> per (image, class) partial sums in the workspace: i = sum sm*y, l = sum sm, r = sum y
+ *                    (sm = softmax(logits)) and the hard-prediction counts i_h, l_h.  The hard prediction is the arg-max of the
+ *                    LOGITS, first maximum winning (as tf.argmax breaks ties) -- not the arg-max of the rounded soft-max, which can
+ *                    tie where the logits do not.
+ *   phx_dice_finish  adds the partials and forms, from the flags of losses.py:8,84-99,
+ *                      dice  (nullable) the table 2 i / (l + r + epsilon) in the shape get_dice returns: [B][C]; [C] with
+ *                            sum_over_batches; [B] with sum_over_labels; one value with both.  use_hard_pred selects the counts.
+ *                      loss  (nullable) dice_loss on the SOFT sums: inv_batch * sum_b (1 - mean_c dice[b][c]) (only_foreground: the mean
+ *                            over c >= 1) -- with inv_batch = 1 / (B * world) a rank's value is its share of the global mean.  With
+ *                            sum_over_batches: inv_batch * B * (1 - mean_c dice[c]), one value for the whole (local) batch.
+ *                      coef  (nullable) [B][C][2] = {alpha, beta}: d loss / d sm[p][c] = alpha[b][c] * y[p][c] + beta[b][c]
+ *                    only_foreground with sum_over_labels is PHX_E_INVAL (the reference slices a label axis that is not there).
+ *   phx_dice_grad    dlogits[p][k] = scale * sm[k] * (g[k] - sum_c g[c] sm[c]), g = alpha y + beta (the soft-max recomputed);
+ *                    add != 0: added to dlogits. */
+size_t phx_dice_ws_bytes(int B, int H, int W, int C);
+int phx_dice_sums(const float* logits, const uint8_t* labels, void* workspace, size_t workspace_bytes, int B, int H, int W, int C,
+                  void* stream);
+int phx_dice_finish(void* workspace, size_t workspace_bytes, int B, int H, int W, int C, int use_hard_pred, int sum_over_labels,
+                    int sum_over_batches, int only_foreground, float epsilon, float inv_batch, float* dice, float* loss, float* coef,
+                    void* stream);
+int phx_dice_grad(const float* logits, const uint8_t* labels, const float* coef, float scale, int add, float* dlogits, int B, int H,
+                  int W, int C, void* stream);
+/* cross_entropy_loss / pixel_wise_cross_entropy_loss_weighted (losses.py:123-159), loss and gradient in one pass + the ordered finish:
+ *   soft-max form   loss = m * sum_p w[label_p] * (logsumexp(x_p) - x_p[label_p]),  m = inv_batch / (H W)  (the mean over all pixels of
+ *                   the global batch);  dlogits = grad_scale * m * w[label_p] * (softmax(x_p) - y_p).  class_weights: DEVICE array [C],
+ *                   NULL = unit weights (cross_entropy_loss)
+ *   use_sigmoid     loss = m / C * sum_{p,c} max(x,0) - x y + log1p(exp(-|x|)),  dlogits = grad_scale * m / C * (sigmoid(x) - y)
+ *                   (class_weights must be NULL)
+ * dlogits NULL: loss only; add != 0: added to dlogits. */
+size_t phx_seg_xent_ws_bytes(int B, int H, int W, int C);
+int phx_seg_xent(const float* logits, const uint8_t* labels, const float* class_weights, int use_sigmoid, float inv_batch,
+                 float grad_scale, int add, float* loss, float* dlogits, void* workspace, size_t workspace_bytes, int B, int H, int W,
+                 int C, void* stream);
+/* adjoint of the NEAREST_NEIGHBOR resize by 2^shift (likelihoods.py:221; shift <= 4): dcoarse[b][y][x][c] (+= if add) the sum of the
+ * 2^shift x 2^shift block of dfine [B][h << shift][w << shift][C]; one thread per coarse element, the block row by row. */
+int phx_nn_resize_adjoint(const float* dfine, float* dcoarse, int B, int h, int w, int C, int shift, int add, void* stream);
+
 /* ---- validation metrics on the device ---------------------------------------------------
  * What phiseg_model._do_validation computes per validation image (phiseg_model.py:586-613 calling
  * utils.generalised_energy_distance utils.py:270-322, utils.variance_ncc_dist utils.py:326-370 and the Dice loop), for I

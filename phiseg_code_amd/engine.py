@@ -193,11 +193,12 @@ class Plan(ForwardLowering, BackwardLowering):
 
     def __init__(self, store, fetches, loss=None, batch=1, training=True, compute_dtype="f32", optimize=True,
                  rng_seed=42, sample_offset=0, loss_inv_batch=None, stream=None, use_hip_graph=True,
-                 split_optimizer=False, n_lanes=None, stamp_tagged=False, fed=(), optimizer=None):
+                 split_optimizer=False, n_lanes=None, stamp_tagged=False, fed=(), optimizer=None, dist_active=False):
         """optimizer: the optimizers.AdamOptimizer / MomentumOptimizer instance the update is lowered from (None: Adam with TF's
         defaults); its slots must be the ones `store` keeps.
         fed: tensors (latents of z_list) whose values the caller feeds (set_input(tensor, array)) instead of having them computed:
-        the plan does not descend through them, so whatever only served them is not launched."""
+        the plan does not descend through them, so whatever only served them is not launched.
+        dist_active: the session runs data parallel -- loss forms that sum over the whole batch (a batch-summed Dice) raise."""
         self.L = rt.lib()
         self.fed = set(fed)
         assert not self.fed or loss is None, "latent feeds are for inference plans"
@@ -215,6 +216,7 @@ class Plan(ForwardLowering, BackwardLowering):
         if self.optimize and optimizers.slot_names(optimizer) != store.slot_names:
             raise ValueError("Plan: the optimizer needs the slots %s, the store keeps %s -- build the ParamStore with the same optimizer"
                              % (optimizers.slot_names(optimizer), store.slot_names))
+        self.dist_active = bool(dist_active)        # data parallel: batch-summed loss forms would need a collective (they raise)
         self.split_optimizer = split_optimizer      # data-parallel: [fwd+bwd] | all-reduce | [optimiser]
         self.use_hip_graph = use_hip_graph and os.environ.get("PHX_HIP_GRAPH", "1") == "1"     # 0: replay the launch list on the lane streams
         # Lanes: independent sub-graphs (posterior / prior encoders, the per-level likelihood chains) are enqueued on
@@ -579,7 +581,7 @@ class Plan(ForwardLowering, BackwardLowering):
                         for g in gops:
                             self.fw_event[g] = ev
                         cross = False
-                if cross or op.type in ("residual_ce", "kl", "weighted_sum"):
+                if cross or op.type in ("residual_ce", "kl", "weighted_sum", "dice_loss", "seg_xent"):
                     self.fw_event[op] = self._record(ln)
         self.n_launch_fwd = len(self.launches)
         self.pending = {}                                    # tensor -> [(buf, (event, lane))]: late grad contributions
@@ -590,7 +592,7 @@ class Plan(ForwardLowering, BackwardLowering):
             for op in bw_ops:
                 if op in self._bw_skip:
                     continue                              # (its backward ran inside a fused group's launch)
-                if any(o in self.grad for o in op.outputs) or op.type in ("residual_ce", "kl", "l2_weights"):
+                if any(o in self.grad for o in op.outputs) or op.type in ("residual_ce", "kl", "l2_weights", "dice_loss", "seg_xent"):
                     self._lane = self.op_lane[op]
                     self._cur_bw_op = op
                     self._wait(self.fw_event.get(op))        # forward of this op may live on another lane's past

@@ -135,16 +135,68 @@ class BackwardLowering:
         pass
 
 
-    _bw_one_hot = _bw_sub_const = _bw_random_normal = _bw_mul = _bw_weighted_sum = _bw_aggregate = _bw_constant = _bw_placeholder
+    _bw_one_hot = _bw_sub_const = _bw_random_normal = _bw_mul = _bw_weighted_sum = _bw_constant = _bw_dice_table = _bw_placeholder
+
+    def _resize_adjoint(self, dfine, dst, add):
+        """dst (a coarse level's gradient, [B, h, w, C] fp32) = / += the 2^s x 2^s block sums of the full-resolution dfine."""
+        B, h, w, C = dst.shape
+        assert dfine.dt == F32 and dst.dt == F32 and dfine.shape[1] % h == 0
+        self._emit(self.L.nn_resize_adjoint, dfine.ptr, dst.ptr, B, h, w, C, (dfine.shape[1] // h).bit_length() - 1, int(add), self.stream)
 
     def _bw_nn_resize(self, op):
-        raise NotImplementedError("nearest-resized logits only feed the fused loss kernel")
+        """Adjoint of the nearest-neighbour view: a FULL-resolution gradient on the resized tensor -> block sums on the stored one
+        (a factor-1 view -- the finest level of likelihoods.phiseg -- hands the buffer on)."""
+        d, src = self.grad[op.outputs[0]], self.val[op.inputs[0]]
+        if op.attrs["shift"] == 0:
+            return self._add_grad(op.inputs[0], buf=d)
+        assert d.shape[1] == src.shape[1] << op.attrs["shift"], "the gradient of a resized tensor is taken at full resolution"
+        self._add_grad(op.inputs[0], write_fn=lambda g: self._resize_adjoint(d, g, False), accum_fn=lambda g: self._resize_adjoint(d, g, True))
 
     def _bw_residual_ce(self, op):
         sv = self.saved.get(op)
         if sv:
+            g = self.grad.get(op.outputs[op.attrs["L"]])
+            if g is not None:
+                # a third-party term (dice_loss, seg_xent) on the summed output s_out = sum_l resize(s_l): its gradient reaches every
+                # level -- added into the buffers this operator's own gradient sits in, before they are passed on
+                for d in sv["dbufs"]:
+                    if d.shape[1] == g.shape[1]:
+                        self._emit(self.L.add_inplace, d.ptr, g.ptr, d.n, F32, self.stream)
+                    else:
+                        self._resize_adjoint(g, d, True)
             for t, d in zip(sv["src"], sv["dbufs"]):
                 self._add_grad(t, buf=d)
+
+    def _bw_aggregate(self, op):
+        """s_out = sum_l resize(s_l): a gradient on the summed logits goes to level 0 as it is and to the coarser levels through the
+        resize adjoint.  (The coarse levels first: the level-0 contribution shares g's buffer, which later contributions may add to.)"""
+        if op.outputs[1] in self.grad:
+            raise NotImplementedError("no backward through the soft-max output of aggregate_logits: take the loss on the logits")
+        g = self.grad.get(op.outputs[0])
+        if g is None:
+            return
+        src = [t.op.inputs[0] if t.op.type == "nn_resize" else t for t in op.inputs]
+        order = sorted(range(len(src)), key=lambda l: self.val[op.inputs[l]].shift == 0)
+        for l in order:
+            if self.val[op.inputs[l]].shift == 0:
+                self._add_grad(src[l], buf=g)
+            else:
+                self._add_grad(src[l], write_fn=lambda d: self._resize_adjoint(g, d, False), accum_fn=lambda d: self._resize_adjoint(g, d, True))
+
+    def _bw_dice_loss(self, op):
+        sv = self.saved.get(op)
+        if sv:
+            lg, lab = self.val[op.inputs[0]], self.val[op.inputs[1]]
+            B, H, W, C = lg.shape
+
+            def emit(g, add):
+                self._emit(self.L.dice_grad, lg.ptr, lab.ptr, sv["coef"].ptr, sv["gscale"], add, g.ptr, B, H, W, C, self.stream)
+            self._add_grad(op.inputs[0], write_fn=lambda g: emit(g, 0), accum_fn=lambda g: emit(g, 1))
+
+    def _bw_seg_xent(self, op):
+        sv = self.saved.get(op)
+        if sv:
+            self._add_grad(op.inputs[0], buf=sv["d"])
 
     def _bw_kl(self, op):
         sv = self.saved.get(op)

@@ -990,6 +990,62 @@ class ForwardLowering:
         self.val[op.outputs[0]] = out
         self._emit(self.L.softmax_xent_map, lg.ptr, lab.ptr, out.ptr, out.n, lg.shape[-1], self.stream)
 
+    # ---- tfwrapper/losses.py (csrc/seg_losses.hip) ------------------------------------------------------------------------------
+    def _seg_loss_args(self, op):
+        lg, lab = self.val[op.inputs[0]], self.val[op.inputs[1]]
+        assert lg.dt == F32 and lg.shift == 0 and lab.dt == U8, "segmentation losses read full-resolution fp32 logits and u8 labels"
+        return lg, lab, lg.shape
+
+    def _dice_launches(self, op, table, loss, coef):
+        """The sums pass and the finishing launch of one Dice operator."""
+        a = op.attrs
+        if a["sum_over_batches"] and self.dist_active:
+            raise NotImplementedError("%s: a batch-summed Dice (macro_robust / sum_over_batches=True) needs a collective over the ranks' "
+                                      "sums, which data-parallel plans do not have" % op.name)
+        lg, lab, (B, H, W, C) = self._seg_loss_args(op)
+        wsb = int(self.L.dice_ws_bytes(B, H, W, C))
+        ws = self._alloc((wsb // 4,), F32)
+        self._emit(self.L.dice_sums, lg.ptr, lab.ptr, ws.ptr, wsb, B, H, W, C, self.stream)
+        self._emit(self.L.dice_finish, ws.ptr, wsb, B, H, W, C, int(a.get("use_hard_pred", False)), int(a["sum_over_labels"]),
+                   int(a["sum_over_batches"]), int(a.get("only_foreground", False)), a["epsilon"], self.inv_batch,
+                   table.ptr if table is not None else None, loss.ptr if loss is not None else None,
+                   coef.ptr if coef is not None else None, self.stream)
+
+    def _fw_dice_loss(self, op, bw):
+        out = self._alloc((), F32)
+        self.val[op.outputs[0]] = out
+        B, _, _, C = self.val[op.inputs[0]].shape
+        w = self.loss_weight.get(op.outputs[0], 0.0) if bw else 0.0
+        coef = self._alloc((B * C * 2,), F32) if (w != 0.0 and self.req.get(op.inputs[0], False)) else None
+        self._dice_launches(op, None, out, coef)
+        if coef is not None:
+            self.saved[op] = dict(coef=coef, gscale=w)
+
+    def _fw_dice_table(self, op, bw):
+        if op.outputs[0] in self.loss_weight:
+            raise ValueError("%s: get_dice is a fetch-only table without a gradient; use dice_loss as a loss term" % op.name)
+        out = self._alloc_like(op.outputs[0])
+        self.val[op.outputs[0]] = out
+        self._dice_launches(op, out, None, None)
+
+    def _fw_seg_xent(self, op, bw):
+        lg, lab, (B, H, W, C) = self._seg_loss_args(op)
+        out = self._alloc((), F32)
+        self.val[op.outputs[0]] = out
+        cw = None
+        if op.attrs["class_weights"] is not None:
+            cw = self._alloc((C,), F32)
+            cw.t.copy_(torch.tensor(op.attrs["class_weights"], dtype=torch.float32))
+            device_sync()
+        w = self.loss_weight.get(op.outputs[0], 0.0) if bw else 0.0
+        d = self._alloc(lg.shape, F32) if (w != 0.0 and self.req.get(op.inputs[0], False)) else None
+        wsb = int(self.L.seg_xent_ws_bytes(B, H, W, C))
+        ws = self._alloc((wsb // 4,), F32)
+        self._emit(self.L.seg_xent, lg.ptr, lab.ptr, cw.ptr if cw is not None else None, int(op.attrs["use_sigmoid"]), self.inv_batch,
+                   w, 0, out.ptr, d.ptr if d is not None else None, ws.ptr, wsb, B, H, W, C, self.stream)
+        if d is not None:
+            self.saved[op] = dict(d=d)
+
     def _fw_kl(self, op, bw):
         mu0, s0, mu1, s1 = [self.val[t] for t in op.inputs]
         grp = self._kl_group

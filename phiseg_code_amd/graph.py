@@ -370,6 +370,63 @@ def softmax_xent_map(logits, labels):
     return get_default_graph().add_op("xent_map", [logits, labels], {}, [(logits.shape[:-1], KIND_F32)], name="eval_xent")[0]
 
 
+# ---- tfwrapper/losses.py: Dice and the cross-entropy family (csrc/seg_losses.hip) ----------------------------------------------
+def _seg_loss_inputs(logits, labels, what):
+    """-> (full-resolution fp32 logits [B,H,W,C], u8 labels [B,H,W]).  `labels` is the u8 class-index tensor or G.one_hot of it (the
+    kernels fold the one-hot into the u8 read); a level stored at a coarser resolution is summed to full resolution first (aggregate_logits)."""
+    if len(logits.shape) == 5:
+        raise NotImplementedError("%s: 3-D (5-D logits) segmentation is not part of this port" % what)
+    if len(logits.shape) != 4 or logits.kind != KIND_F32 or not 2 <= logits.shape[3] <= 8:
+        raise ValueError("%s: logits must be an fp32 [B, H, W, C] tensor (a logit head) with 2 <= C <= 8, got %r" % (what, logits))
+    if labels.kind != KIND_U8 and labels.op is not None and labels.op.type == "one_hot":
+        if labels.op.attrs["depth"] != logits.shape[3]:
+            raise ValueError("%s: labels are one-hot of depth %d, the logits have %d classes" % (what, labels.op.attrs["depth"], logits.shape[3]))
+        labels = labels.op.inputs[0]
+    if labels.kind != KIND_U8:
+        raise NotImplementedError("%s: float one-hot / soft label tensors are not supported -- the loss kernels fold the one-hot into "
+                                  "the read of u8 class indices and have no dense label read; pass the u8 [B, H, W] tensor or "
+                                  "G.one_hot of it" % what)
+    if tuple(labels.shape) != tuple(logits.shape[:3]):
+        raise ValueError("%s: labels %s do not match logits %s" % (what, labels.shape, logits.shape))
+    if logits.op is not None and logits.op.type == "nn_resize" and logits.op.attrs["shift"] > 0:
+        logits = aggregate_logits([logits])[0]           # (a level stored at a coarser resolution: materialised; shift 0 is a plain view)
+    return logits, labels
+
+
+def dice_loss(logits, labels, epsilon=1e-10, sum_over_labels=False, sum_over_batches=False, only_foreground=False):
+    """tfwrapper/losses.py:50-119 with the mode resolved to its flags: 1 - mean of the soft Dice -> scalar, differentiable."""
+    if only_foreground and sum_over_labels:
+        raise ValueError("dice_loss: only_foreground slices a label axis that sum_over_labels removed (the reference fails there too)")
+    logits, labels = _seg_loss_inputs(logits, labels, "dice_loss")
+    attrs = dict(epsilon=float(epsilon), sum_over_labels=bool(sum_over_labels), sum_over_batches=bool(sum_over_batches),
+                 only_foreground=bool(only_foreground))
+    return get_default_graph().add_op("dice_loss", [logits, labels], attrs, [((), KIND_F32)], name="dice_loss")[0]
+
+
+def dice_table(logits, labels, epsilon=1e-10, sum_over_labels=False, sum_over_batches=False, use_hard_pred=True):
+    """tfwrapper/losses.py:8-47 get_dice -> [B, C]; [C] with sum_over_batches; [B] with sum_over_labels; a scalar with both.
+    Fetch-only: no gradient, and not a term of a loss."""
+    logits, labels = _seg_loss_inputs(logits, labels, "get_dice")
+    shape = (() if sum_over_batches else (logits.shape[0],)) + (() if sum_over_labels else (logits.shape[3],))
+    attrs = dict(epsilon=float(epsilon), sum_over_labels=bool(sum_over_labels), sum_over_batches=bool(sum_over_batches),
+                 use_hard_pred=bool(use_hard_pred))
+    return get_default_graph().add_op("dice_table", [logits, labels], attrs, [(shape, KIND_F32)], name="dice")[0]
+
+
+def seg_xent(logits, labels, class_weights=None, use_sigmoid=False):
+    """tfwrapper/losses.py:123-159: mean soft-max cross-entropy over all pixels, optionally weighted per class, or the mean sigmoid
+    cross-entropy over all pixels and classes -> scalar, differentiable."""
+    logits, labels = _seg_loss_inputs(logits, labels, "cross_entropy_loss")
+    if class_weights is not None:
+        class_weights = [float(w) for w in class_weights]
+        if use_sigmoid:
+            raise ValueError("seg_xent: class weights belong to the soft-max form")
+        if len(class_weights) != logits.shape[3]:
+            raise ValueError("pixel_wise_cross_entropy_loss_weighted: %d class weights for %d classes" % (len(class_weights), logits.shape[3]))
+    return get_default_graph().add_op("seg_xent", [logits, labels], dict(class_weights=class_weights, use_sigmoid=bool(use_sigmoid)),
+                                      [((), KIND_F32)], name="seg_xent")[0]
+
+
 def weighted_sum(scalars, weights):
     return get_default_graph().add_op("weighted_sum", list(scalars), dict(weights=[float(w) for w in weights]),
                                       [((), KIND_F32)], name="loss_tot")[0]

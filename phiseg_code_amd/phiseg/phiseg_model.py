@@ -80,7 +80,7 @@ class Session:
                 store, fetch_tensors, loss=self.model.loss_tot if train else None, batch=batch, training=training,
                 compute_dtype=self.compute_dtype, rng_seed=self.rng_seed, sample_offset=rank * batch,
                 loss_inv_batch=1.0 / (batch * world), split_optimizer=bool(self.dist and self.dist.active), stamp_tagged=stamp_tagged,
-                fed=fed, optimizer=self.model.optimizer)
+                fed=fed, optimizer=self.model.optimizer, dist_active=bool(self.dist and self.dist.active))
         return self.plans[key]
 
     def latent_feeds(self, feed_dict):
@@ -241,6 +241,7 @@ class phiseg():
             self.loss_dict['weight_decay'] = wd
             terms.append(wd)
             weights.append(1.0)
+        self._loss_terms, self._loss_weights = terms, weights       # add_loss_term() rebuilds loss_tot from these
         self.loss_tot = G.weighted_sum(terms, weights)
         self.loss_dict['total_loss'] = self.loss_tot
         self.optimizer = self._make_optimizer(exp_config)
@@ -256,6 +257,32 @@ class phiseg():
 
     def checks(self):
         pass
+
+    def add_loss_term(self, name, scalar, weight=1.0):
+        """Add a scalar of the caller's making (tfwrapper.losses.dice_loss, cross_entropy_loss, ... on a tensor of this model) to the
+        objective: loss_dict[name] = scalar, and loss_tot, loss_dict['total_loss'] and train_step are rebuilt as the weighted sum of the
+        old terms plus weight * scalar -- so optimizer.minimize (train_step) follows the new objective.  Legal only before the session
+        has compiled a plan or created its ParamStore: the live-variable set and the plans are keyed on the old loss."""
+        if self.sess.store is not None or self.sess.plans:
+            raise RuntimeError("add_loss_term(%r): the session has already created its parameter store or compiled a plan for the "
+                               "old loss -- add loss terms before the first sess.run / set_weights" % (name,))
+        if not isinstance(scalar, G.Tensor) or scalar.shape != ():
+            raise ValueError("add_loss_term(%r): the term must be a scalar graph tensor, got %r" % (name, scalar))
+        if scalar.op.type == "dice_table":
+            raise ValueError("add_loss_term(%r): get_dice is a fetch-only table without a gradient; use dice_loss" % (name,))
+        if name in self.loss_dict:
+            raise ValueError("add_loss_term: loss_dict already has an entry %r" % (name,))
+        if self.dist is not None and self.dist.active and scalar.op.attrs.get("sum_over_batches", False):
+            raise NotImplementedError("add_loss_term(%r): a batch-summed Dice (macro_robust / sum_over_batches=True) needs a collective "
+                                      "over the ranks' sums, which data-parallel training does not have" % (name,))
+        G.set_default_graph(self.graph)
+        self._loss_terms = self._loss_terms + [scalar]
+        self._loss_weights = self._loss_weights + [float(weight)]
+        self.loss_dict[name] = scalar
+        self.loss_tot = G.weighted_sum(self._loss_terms, self._loss_weights)
+        self.loss_dict['total_loss'] = self.loss_tot
+        self.train_step = TrainStep(self.loss_tot)
+        return scalar
 
     def _make_optimizer(self, exp_config):
         """phiseg_model.py:135-141: Momentum is instantiated with momentum 0.9 and Nesterov's form, anything else with the learning
