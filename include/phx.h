@@ -383,6 +383,40 @@ int phx_bn_wide_fwd(const float* xs, int nz, float* xsum, const float* gamma, co
 int phx_bn_wide_bwd(const void* dA, const float* dA_slices, int nzd, const float* x, const float* scale, const float* shift,
                     const float* mean, const float* rstd, const float* gamma, void* dx, float* dgamma, float* dbeta, int P, int C,
                     int act, void* stream);
+/* Batch renormalisation, training mode (tfwrapper/normalisation.py:72-142 = tf.contrib.layers.batch_norm(renorm=True); csrc/norm_renorm.hip).
+ * Per channel, with (mu, var) the biased batch moments, sigma = sqrt(var + eps) and t = *step_dev read ON THE DEVICE (the optimiser
+ * step counter: a captured graph follows the clipping schedule across replays):
+ *   r = min(sigma / (renorm_stddev + (1 - renorm_stddev_weight) sigma), rmax(t))                        (no lower clip)
+ *   d = clip((mu - renorm_mean - (1 - renorm_mean_weight) mu) / (renorm_stddev + (1 - renorm_stddev_weight) sigma), +-dmax(t))
+ *   y = act(gamma ((x - mu) / sigma * r + d) + beta);  rmax: 1 up to t = 500, linear to 3 at t = 4000;  dmax: 0 up to 500, linear to 5 at 2500.
+ * Both forward entry points only READ the four renorm variables and publish mean, rstd = 1 / sigma, scale = gamma r rstd,
+ * shift = beta + gamma d - mean scale, r, d and gamma_eff = gamma r ([C] fp32 each).  With r and d constant for the gradient the layer is
+ * batch norm with gamma_eff: every batch-norm backward entry point serves it when handed gamma_eff in place of gamma.
+ *   phx_renorm_apply_fused  any P, C <= 2048 (C % 8 != 0: C <= 256), fp32 / bf16 in and out; sums [C][2] as phx_norm_stats (with pivot) or
+ *                           phx_norm_reduce_partials (pivot NULL) leave them.  A null pointer other than pivot: PHX_E_INVAL.
+ *   phx_renorm_small_fwd    the whole forward in one launch for 1 <= P <= 4096 and C % 8 == 0 (a block owns eight channels of all
+ *                           pixels, exact two-pass variance); anything else is PHX_E_INVAL and nothing is launched.
+ *   phx_renorm_tail_multi   ONE launch per training step over n device records (one block per layer):
+ *                             { const float *mean, *rstd, *r, *d, *dgs, *dbs; float *dgamma, *dbeta, *renorm_mean, *renorm_mean_weight,
+ *                               *renorm_stddev, *renorm_stddev_weight, *moving_mean, *moving_var; int C; float eps, renorm_momentum,
+ *                               moving_momentum; }     (phx_renorm_tail_desc_bytes() bytes each; momentum = 1 - decay)
+ *                           dgamma += r dgs + d dbs, dbeta += dbs (dgs / dbs: what the backward kernels accumulated for gamma_eff; both
+ *                           NULL: no gradient), then with assign(v, x, m): v -= (v - x) m
+ *                             assign(renorm_mean, mean, rm); assign(renorm_mean_weight, 1, rm); assign(renorm_stddev, 1 / rstd, rm);
+ *                             assign(renorm_stddev_weight, 1, rm); assign(moving_mean, renorm_mean / renorm_mean_weight, mm);
+ *                             assign(moving_var, (renorm_stddev / renorm_stddev_weight)^2 - eps, mm)      (updated values on the right).
+ *                           The state is written by this launch only -- after every reader of the step. */
+int phx_renorm_apply_fused(const void* x, int x_dt, const float* sums, const float* pivot, const float* gamma, const float* beta, float eps,
+                           void* y, int y_dt, float* mean, float* rstd, float* scale, float* shift, float* r, float* d, float* gamma_eff,
+                           const float* renorm_mean, const float* renorm_mean_weight, const float* renorm_stddev,
+                           const float* renorm_stddev_weight, const int32_t* step_dev, int P, int C, int act, void* stream);
+int phx_renorm_small_supported(int P, int C, int x_dt, int y_dt);
+int phx_renorm_small_fwd(const void* x, int x_dt, const float* gamma, const float* beta, float eps, void* y, int y_dt, float* mean,
+                         float* rstd, float* scale, float* shift, float* r, float* d, float* gamma_eff, const float* renorm_mean,
+                         const float* renorm_mean_weight, const float* renorm_stddev, const float* renorm_stddev_weight,
+                         const int32_t* step_dev, int P, int C, int act, void* stream);
+int phx_renorm_tail_desc_bytes(void);
+int phx_renorm_tail_multi(const void* descs_dev, int n, void* stream);
 /* Group / instance norm (tfwrapper/normalisation.py:3-36), bf16 NHWC, the whole layer in ONE launch when a sample has
  * P = H*W <= 256 pixels (maps up to 16 x 16) and the statistic is per channel (G == C: instance norm) or per 16-channel
  * group (G * 16 == C: group_norm2D's default groups for C >= 32): a wave owns (sample, 16-channel slice) pairs, keeps the

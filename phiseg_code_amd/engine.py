@@ -257,6 +257,7 @@ class Plan(ForwardLowering, BackwardLowering):
         self._pack_jobs = []          # (w, wpk_fwd, wpk_dgrad, Cin, Cin_pad, Cout): ONE multi-filter pack launch per run
         self._barriers = []           # grid-barrier words of the one-launch kernels (zero arena): word 288 != 0 = that barrier timed out
         self._wpk32, self._pack32_jobs = {}, []     # fp32 plans: packed fp32 filters of the fp32 matrix kernels, [w, wpk_fwd, wpk_dgrad, Cin, Cout]
+        self._renorm_jobs = []        # (saved record, norm variables, C) of every training-mode batch-renorm layer: ONE tail launch per step
         self._bninfer_jobs = []       # (gamma, beta, moving_mean, moving_var, scale, shift, C, eps): ONE launch per run
         self._zarena = torch.zeros(8 << 20, dtype=torch.float32, device=_device())     # 32 MB of per-step accumulators
         self._zused = 0
@@ -364,6 +365,27 @@ class Plan(ForwardLowering, BackwardLowering):
             self._keep.append(desc)
             self._emit(self.L.head1x1_wgrad_multi, desc.data_ptr(), len(jobs), blk, xdt, nout, lds, self.stream)
         self._wgm_jobs, self._wgr_jobs, self._tail_jobs, self._headw_jobs = {}, [], [], {}
+
+    def _emit_renorm_tail(self):
+        """Batch renormalisation, plans with a loss: ONE launch behind the whole backward pass (lane 0, after the join) adds every renorm
+        layer's corrected dgamma / dbeta into the gradient arena -- before the optimiser and the gradient exchange read it -- and applies the
+        layer's six state updates from its saved mean / rstd.  The forward launches only read that state, so within a step every read
+        precedes every write."""
+        if not self._renorm_jobs:
+            return
+        st = self.store
+        rec = np.zeros(len(self._renorm_jobs), dtype=[(n, "<u8") for n in ("mean", "rstd", "r", "d", "dgs", "dbs", "dgamma", "dbeta", "rmean", "rmean_w",
+                                                                         "rstddev", "rstddev_w", "mmean", "mvar")]
+                       + [("C", "<i4"), ("eps", "<f4"), ("renorm_momentum", "<f4"), ("moving_momentum", "<f4")])
+        assert rec.dtype.itemsize == int(self.L.renorm_tail_desc_bytes()), "RenormTailDesc layout mismatch (csrc/norm_renorm.hip vs engine.py)"
+        for i, (sv, nv, C) in enumerate(self._renorm_jobs):
+            rn = sv.renorm
+            rec[i] = (sv.mean.ptr, sv.rstd.ptr, rn.r.ptr, rn.d.ptr, rn.dgs.ptr, rn.dbs.ptr, st.grad_ptr(nv["gamma"]), st.grad_ptr(nv["beta"]),
+                      *[st.ptr(nv[k]) for k in tfnorm.RENORM_STATE], st.ptr(nv["moving_mean"]), st.ptr(nv["moving_variance"]), C,
+                      tfnorm.EPS["renorm"], 1.0 - tfnorm.RENORM_DECAY, 1.0 - tfnorm.RENORM_MOVING_DECAY)
+        self._renorm_desc = torch.from_numpy(rec.view(np.uint8).copy()).to(_device())
+        self._keep.append(self._renorm_desc)
+        self._emit(self.L.renorm_tail_multi, self._renorm_desc.data_ptr(), len(self._renorm_jobs), self.stream)
 
     def _prune_dead_event_records(self):
         """Every gradient contribution records an event in case another lane folds it in; most are consumed on the lane
@@ -610,6 +632,7 @@ class Plan(ForwardLowering, BackwardLowering):
                 self._wait(evl)
         self._lane = 0
         self._emit_deferred()
+        self._emit_renorm_tail()
         self._prune_dead_event_records()
         self.launches[0] = (self.L.memset, (self._zarena.data_ptr(), 0, max(self._zused, 1) * 4, self.stream))
         if self._pack_jobs:           # slot 1 was reserved before the fork: refresh every packed bf16 filter in one launch

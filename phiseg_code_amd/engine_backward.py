@@ -269,6 +269,15 @@ class BackwardLowering:
             else:
                 self._add_grad(t, write_fn=lambda g: self._emit(self.L.memcpy_d2d, g.ptr, d.ptr, d.nbytes, self.stream))
 
+    def _norm_grad_ptrs(self, sv, nv):
+        """(gamma, dgamma, dbeta) pointers the norm backward kernels take.  A batch-renorm layer hands them gamma_eff = gamma * r and its
+        per-layer scratch: with r and d constant the layer is batch norm with gamma_eff, and the step's tail launch forms the parameter
+        gradients dgamma = r dgamma' + d dbeta', dbeta = dbeta' from the scratch (Plan._emit_renorm_tail)."""
+        rn = sv.renorm
+        if rn is not None:
+            return rn.gamma_eff.ptr, rn.dgs.ptr, rn.dbs.ptr
+        return self.store.ptr(nv["gamma"]), self.store.grad_ptr(nv["gamma"]), self.store.grad_ptr(nv["beta"])
+
     def _norm_bwd(self, sv, nv, dA, dY, C, act, nrep, sums2, bias=None, tagged=False, s2d=(), rider=None):
         """Generic normalisation backward: the reduction over (dA, y), then the fused apply that writes dY and adds dgamma / dbeta.
         bias: (forward sums, forward pivot, db) pointers of the closed-form conv-bias gradient (phx_norm_bwd_apply_fused_bias and the
@@ -276,6 +285,7 @@ class BackwardLowering:
         permutation.  A HeadGrad dA is formed on the fly (dy_head w_head^T).  rider: the filter / bias gradient of that head
         (_head_rider_for) rides on the pair; where the pair cannot carry it, its job goes back to the heads' own launch."""
         Lb, y = self.L, sv.y
+        gamma_p, dgamma_p, dbeta_p = self._norm_grad_ptrs(sv, nv)
         if rider is not None:
             ok = (isinstance(dA, HeadGrad) and dA.dy.ptr == rider["dy"] and dA.nout == rider["nout"] and not s2d
                   and (bias is None or bias[2] is None) and sv.NS == 1 and sv.G == C and y.dt == BF16 and dY.dt == BF16)
@@ -286,8 +296,8 @@ class BackwardLowering:
                 lead = (None, rider["dy"], dA.w_ptr, rider["nout"], y.ptr, sv.scale.ptr, sv.shift.ptr, sv.mean.ptr, sv.rstd.ptr)
                 self._emit(Lb.norm_bwd_reduce_rider, *lead, sums2.ptr, hacc.ptr, sv.P, C, act, nrep, self.stream,
                            tag="bytes_norm_bwd_reduce" if tagged else None, flops=float(y.nbytes))
-                self._emit(Lb.norm_bwd_apply_fused_rider, *lead, self.store.ptr(nv["gamma"]), sums2.ptr, dY.ptr, self.store.grad_ptr(nv["gamma"]),
-                           self.store.grad_ptr(nv["beta"]), hacc.ptr, rider["dw"], rider["db"], sv.P, C, act, nrep, self.stream,
+                self._emit(Lb.norm_bwd_apply_fused_rider, *lead, gamma_p, sums2.ptr, dY.ptr, dgamma_p,
+                           dbeta_p, hacc.ptr, rider["dw"], rider["db"], sv.P, C, act, nrep, self.stream,
                            tag="bytes_norm_bwd_apply" if tagged else None, flops=float(y.nbytes + dY.nbytes))
                 return
         if isinstance(dA, HeadGrad):
@@ -300,8 +310,8 @@ class BackwardLowering:
         lead += (sv.scale.ptr, sv.shift.ptr, sv.mean.ptr, sv.rstd.ptr)
         dims = (sv.NS, sv.P, C, sv.G, act, nrep, *s2d, self.stream)
         self._emit(reduce, *lead, sums2.ptr, *dims, tag="bytes_norm_bwd_reduce" if tagged else None, flops=float(nb + y.nbytes))
-        self._emit(apply, *lead, self.store.ptr(nv["gamma"]), sums2.ptr, dY.ptr, *ydt, self.store.grad_ptr(nv["gamma"]),
-                   self.store.grad_ptr(nv["beta"]), *(bias or ()), *dims,
+        self._emit(apply, *lead, gamma_p, sums2.ptr, dY.ptr, *ydt, dgamma_p,
+                   dbeta_p, *(bias or ()), *dims,
                    tag="bytes_norm_bwd_apply" if tagged else None, flops=float(nb + y.nbytes + dY.nbytes))
 
     def _bw_norm_act(self, op):
@@ -390,14 +400,15 @@ class BackwardLowering:
             raise NotImplementedError("backward through inference-mode batch norm is not on the hot path")
         R = NormRoute
         one_launch = {R.BN_WIDE: self._bw_norm_bn_wide, R.BN_SMALL_F32Y: self._bw_norm_bn_small, R.BN_SMALL: self._bw_norm_bn_small,
-                      R.FGN: self._bw_norm_small, R.NORM_SMALL: self._bw_norm_small}.get(sv.route) if dA.dt == BF16 else None
+                      R.FGN: self._bw_norm_small, R.NORM_SMALL: self._bw_norm_small, R.RENORM_SMALL: self._bw_norm_bn_small}.get(sv.route) if dA.dt == BF16 else None
+        if sv.route is R.RENORM_SMALL and not self.L.bn_small_supported(sv.P, sv.y.shape[3], BF16):
+            one_launch = None            # (phx_bn_small_bwd owns 16 channels per block, phx_renorm_small_fwd eight: C % 16 != 0 goes the generic way)
         return (one_launch or self._bw_norm_generic)(op, sv, dA, act)
 
     def _bw_one_launch_args(self, op, sv, dY):
         """(saved statistics..., gamma, dY, dgamma, dbeta): the argument run the one-launch norm backward kernels share."""
-        nv = op.attrs["norm_vars"]
-        return (sv.scale.ptr, sv.shift.ptr, sv.mean.ptr, sv.rstd.ptr, self.store.ptr(nv["gamma"]), dY.ptr, self.store.grad_ptr(nv["gamma"]),
-                self.store.grad_ptr(nv["beta"]))
+        gamma_p, dgamma_p, dbeta_p = self._norm_grad_ptrs(sv, op.attrs["norm_vars"])
+        return (sv.scale.ptr, sv.shift.ptr, sv.mean.ptr, sv.rstd.ptr, gamma_p, dY.ptr, dgamma_p, dbeta_p)
 
     def _bw_norm_bn_wide(self, op, sv, dA, act):
         y, dY = sv.y, self._alloc(sv.y.shape, BF16)

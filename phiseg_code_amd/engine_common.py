@@ -11,7 +11,7 @@ from phiseg_code_amd import graph as G
 from phiseg_code_amd import runtime as rt
 from phiseg_code_amd.tfwrapper import normalisation as tfnorm
 
-__all__ = ['F32', 'BF16', 'U8', '_TORCH_DT', '_NP_DT', '_ESIZE', '_LIK_SIDE_MAXLVL', '_WGRAD_DEFER_BLOCKS', '_NREP', '_NREP_MINP', '_STAMPS', '_DETERMINISTIC', '_BN_SMALL', '_BN_SMALL_F32', '_BN_WIDE', '_BN_WIDE_MAXLINES', '_SKIP_HEAD_A', '_POOL_FUSE', '_xf_enabled', '_upconv_min_h', 'UpBuf', '_fgn_mode', '_dual_enabled', '_f32_mfma_enabled', '_recomb_enabled', '_onepass_enabled', '_head_rider_enabled', '_HEAD_RIDER_NOUT', '_noop', '_device', 'live_variables', 'device_sync', 'Buf', 'DualBuf', 'HeadGrad', 'SliceGrad', 'XfBuf', 'NormRoute', 'StatsSource', 'ConvSaved']
+__all__ = ['F32', 'BF16', 'U8', '_TORCH_DT', '_NP_DT', '_ESIZE', '_LIK_SIDE_MAXLVL', '_WGRAD_DEFER_BLOCKS', '_NREP', '_NREP_MINP', '_STAMPS', '_DETERMINISTIC', '_BN_SMALL', '_BN_SMALL_F32', '_BN_WIDE', '_BN_WIDE_MAXLINES', '_SKIP_HEAD_A', '_POOL_FUSE', '_xf_enabled', '_upconv_min_h', 'UpBuf', '_fgn_mode', '_dual_enabled', '_f32_mfma_enabled', '_recomb_enabled', '_onepass_enabled', '_head_rider_enabled', '_HEAD_RIDER_NOUT', '_noop', '_device', 'live_variables', 'device_sync', 'Buf', 'DualBuf', 'HeadGrad', 'SliceGrad', 'XfBuf', 'NormRoute', 'StatsSource', 'ConvSaved', 'RenormSaved']
 
 F32, BF16, U8 = rt.F32, rt.BF16, 2
 _TORCH_DT = {F32: torch.float32, BF16: torch.bfloat16, U8: torch.uint8}
@@ -206,9 +206,19 @@ class UpBuf:
         return self.n * _ESIZE[self.dt]
 
 
+class RenormSaved:
+    """What a training-mode batch-renorm layer adds to its saved record: the per-channel r, d and gamma_eff = gamma * r its forward
+    launch publishes, and -- in a plan with a loss -- the scratch (dgs, dbs) from the step's zero arena the backward kernels accumulate
+    the gradients of gamma_eff / the shift into; the step's tail launch (phx_renorm_tail_multi) turns them into dgamma / dbeta."""
+    __slots__ = ("r", "d", "gamma_eff", "dgs", "dbs")
+
+    def __init__(self, r, d, gamma_eff, dgs=None, dbs=None):
+        self.r, self.d, self.gamma_eff, self.dgs, self.dbs = r, d, gamma_eff, dgs, dbs
+
+
 class NormRoute(enum.Enum):
     """How a conv unit's normalisation is lowered (engine_forward.conv_norm_route chooses; DESIGN.md section 1 has the table)."""
-    NONE, INFER_FOLDED, INFER, BN_WIDE, BN_SMALL_F32Y, BN_SMALL, FGN, NORM_SMALL, GENERIC = range(9)
+    NONE, INFER_FOLDED, INFER, BN_WIDE, BN_SMALL_F32Y, BN_SMALL, FGN, NORM_SMALL, GENERIC, RENORM_SMALL = range(10)
 
 
 class StatsSource(enum.Enum):
@@ -218,10 +228,10 @@ class StatsSource(enum.Enum):
 
 class ConvSaved:
     """What the forward lowering of a conv_unit / transposed / general unit / norm_act leaves for the backward pass (Plan.saved[op]).
-    An unknown attribute raises on read and on write."""
+    An unknown attribute raises on read and on write.  renorm: a training-mode batch-renorm layer's RenormSaved, None otherwise."""
     _OPTIONAL = dict(route=NormRoute.NONE, y=None, scale=None, shift=None, mean=None, rstd=None, NS=None, P=None, G=None, wd_pad=None,
                      upconv=None, a_unwritten=None, fsums=None, fpivot=None, transposed=None, general=None, geo=None, f32m=False,
-                     norm_head=False, latent=False)
+                     norm_head=False, latent=False, renorm=None)
     __slots__ = ("x", "out", "norm", "mfma", "padded", "cin_eff", "k1", "head1x1") + tuple(_OPTIONAL)
 
     def __init__(self, x, out, norm, mfma, padded, cin_eff, k1, head1x1, **optional):

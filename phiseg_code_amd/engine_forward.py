@@ -23,35 +23,41 @@ def conv_norm_route(Lb, norm, training, bw, act_dt, x_dt, y_dt, out_dt, B, H, Wd
     fgn = _fgn_mode() if fgn is None else fgn
     if norm is None:
         return NormRoute.NONE, None
-    NS, P = (1, B * H * Wd) if norm == "batch" else (B, H * Wd)
+    per_batch = norm in ("batch", "renorm")        # statistics over the whole batch (NS = 1)
+    NS, P = (1, B * H * Wd) if per_batch else (B, H * Wd)
     if norm == "batch" and not training:
         return (NormRoute.INFER_FOLDED if (mfma and not head1x1 and not bw) else NormRoute.INFER), None
     both_bf16 = y_dt == BF16 and out_dt == BF16
+    if norm == "renorm" and both_bf16 and P <= _BN_SMALL and Lb.renorm_small_supported(P, cout, y_dt, out_dt):
+        # training-mode batch renormalisation (an inference-mode layer arrives here as batch norm): one launch on the H <= 8 levels of a
+        # bf16 plan -- where batch norm has its one-launch forms -- else the generic route with batch norm's statistics source (an fp32
+        # plan with a fresh state then computes what the batch-norm plan computes, bit for bit); no pool / head / depth-to-space / wide / xf form
+        return NormRoute.RENORM_SMALL, None
     if norm == "batch" and both_bf16 and P <= _BN_SMALL and Lb.bn_small_supported(P, cout, BF16):
         if mfma and not head1x1 and _BN_SMALL_F32 and Lb.conv3x3_mfma_f32out_supported(B, H, Wd, cin_eff, cout):
             nz = int(Lb.conv3x3_mfma_ksplit(B, H, Wd, cin_eff, cout))
             wide = bool(_BN_WIDE and Lb.bn_wide_supported(P, cout) and P * nz <= _BN_WIDE_MAXLINES)
             return (NormRoute.BN_WIDE if wide else NormRoute.BN_SMALL_F32Y), None
         return NormRoute.BN_SMALL, None
-    if (norm != "batch" and mfma and not head1x1 and not concat_free and not deterministic and (fgn >= 2 or (fgn == 1 and Gn != cout))
+    if (not per_batch and mfma and not head1x1 and not concat_free and not deterministic and (fgn >= 2 or (fgn == 1 and Gn != cout))
             and both_bf16 and x_dt == BF16 and Lb.conv3x3_fgn_supported(B, H, Wd, cin_eff, cout, Gn)
             and Lb.norm_small_supported(NS, P, cout, Gn, BF16)):
         return NormRoute.FGN, None
-    if norm != "batch" and both_bf16 and Lb.norm_small_supported(NS, P, cout, Gn, BF16):
+    if not per_batch and both_bf16 and Lb.norm_small_supported(NS, P, cout, Gn, BF16):
         return NormRoute.NORM_SMALL, None
     small = P <= 16384 or act_dt == F32
     tiles = Lb.conv3x3_mfma_bf16_tiles_dual if concat_free else Lb.conv3x3_mfma_bf16_tiles
     if upsampled:
         stats = StatsSource.PIVOT_PASS
-    elif norm == "batch" and mfma and not small:
+    elif per_batch and mfma and not small:
         stats = StatsSource.PARTIALS
-    elif (norm == "batch" and mfma and small and not deterministic and not head1x1 and act_dt == BF16
+    elif (per_batch and mfma and small and not deterministic and not head1x1 and act_dt == BF16
           and Lb.conv3x3_mfma_stats_atomic_supported(B, H, Wd, cin_eff, cout)):
         stats = StatsSource.ATOMIC
-    elif (norm != "batch" and mfma and not head1x1 and act_dt == BF16 and H % 16 == 0 and Wd % 16 == 0
+    elif (not per_batch and mfma and not head1x1 and act_dt == BF16 and H % 16 == 0 and Wd % 16 == 0
           and int(tiles(B, H, Wd, cin_eff, cout)) % B == 0):
         stats = StatsSource.PARTIALS_NS
-    elif norm == "batch" and not small and not deterministic:
+    elif per_batch and not small and not deterministic:
         stats = StatsSource.DIRECT
     else:
         stats = StatsSource.PIVOT_PASS
@@ -171,13 +177,41 @@ class ForwardLowering:
     def _norm_vectors(self, sv, B, HW, C, num_groups):
         """Statistics geometry of sv.norm on a [B, HW, C] tensor -- NS statistics sets of P values per channel, G groups -- and the
         four per-layer vectors, all recorded on `sv`."""
-        if sv.norm == "batch":
+        if sv.norm in ("batch", "renorm"):
             sv.NS, sv.P, sv.G = 1, B * HW, C
         else:
             sv.G = C if sv.norm == "instance" else (num_groups or max(2, C // 16))
             sv.NS, sv.P = B, HW
         sv.scale, sv.shift = self._alloc((sv.NS * C,), F32), self._alloc((sv.NS * C,), F32)
         sv.mean, sv.rstd = self._alloc((sv.NS * sv.G,), F32), self._alloc((sv.NS * sv.G,), F32)
+
+    @staticmethod
+    def _lowered_norm(a, training):
+        """The normalisation kind a unit is lowered as: batch renormalisation in inference mode IS inference-mode batch norm (r = 1, d = 0,
+        the moving statistics) and takes its routes and kernels; only a training-mode layer is "renorm"."""
+        return "batch" if (a["norm"] == "renorm" and not training) else a["norm"]
+
+    def _renorm_setup(self, sv, nv, C):
+        """A training-mode batch-renorm layer: the vectors its forward launch publishes beside mean / rstd / scale / shift and, in a plan
+        with a loss, the gradient scratch and the layer's record of the step's tail launch (Plan._emit_renorm_tail)."""
+        rn = sv.renorm = RenormSaved(self._alloc((C,), F32), self._alloc((C,), F32), self._alloc((C,), F32))
+        if self.loss is not None:
+            if any(j[1]["renorm_mean"] is nv["renorm_mean"] for j in self._renorm_jobs):
+                raise NotImplementedError("batch_renorm: two training-mode instances of the layer %s in one plan would read and update the "
+                                          "same renorm state within one step" % nv["renorm_mean"].name.rsplit("/", 1)[0])
+            rn.dgs, rn.dbs = self._alloc_zeroed(C), self._alloc_zeroed(C)
+            self._renorm_jobs.append((sv, nv, C))
+
+    def _renorm_args(self, sv, nv):
+        """(r, d, gamma_eff, the four renorm variables, the step counter): the arguments the renorm forward entry points add.  The clip
+        bounds follow the optimiser step, read on the device: a captured graph walks the schedule with no host value baked in."""
+        rn, st = sv.renorm, self.store
+        return (rn.r.ptr, rn.d.ptr, rn.gamma_eff.ptr, *[st.ptr(nv[k]) for k in tfnorm.RENORM_STATE], st.step.data_ptr())
+
+    def _renorm_apply(self, sv, nv, y, sums, pivot, out, C, act):
+        self._emit(self.L.renorm_apply_fused, y.ptr, y.dt, sums.ptr, pivot.ptr if pivot is not None else None, self.store.ptr(nv["gamma"]),
+                   self.store.ptr(nv["beta"]), tfnorm.EPS["renorm"], out.ptr, out.dt, sv.mean.ptr, sv.rstd.ptr, sv.scale.ptr, sv.shift.ptr,
+                   *self._renorm_args(sv, nv), sv.P, C, act, self.stream, tag="bytes_norm_apply", flops=float(y.nbytes + out.nbytes))
 
     def _moving_args(self, nv, upd):
         """(moving mean, moving variance, momentum) arguments: the moving statistics move only in a training plan's batch norm."""
@@ -211,6 +245,9 @@ class ForwardLowering:
             return
         sums = self._alloc_zeroed(sv.NS * C * 2)
         pivot = self._norm_stats_pass(sv, y, sums, C, conv)
+        if sv.norm == "renorm":
+            self._renorm_setup(sv, nv, C)
+            return self._renorm_apply(sv, nv, y, sums, pivot, out, C, act)
         self._emit(Lb.norm_apply_fused, *self._norm_apply_args(sv, a, y, sums, pivot, out, C, act, training), S)
 
     def _fw_tconv_unit(self, op, bw):
@@ -235,8 +272,8 @@ class ForwardLowering:
         out = self._alloc_like(op.outputs[0])
         self.val[op.outputs[0]] = out
         act = rt.ACT_CODES[a["act"]]
-        norm = a["norm"]
         training = a["training"] if isinstance(a["training"], bool) else self.training
+        norm = self._lowered_norm(a, training)
         wptr, bptr = self.store.ptr(W), (self.store.ptr(b) if b is not None else None)
         sv = self.saved[op] = ConvSaved.plain(x, out, norm, cin, transposed=a.get("transposed"), general=a.get("general"), geo=geo)
         if norm is None:
@@ -346,7 +383,7 @@ class ForwardLowering:
                     break
                 a = u.attrs
                 training = a["training"] if isinstance(a["training"], bool) else self.training
-                norm_ok = (a["norm"] == "batch" and not training and a["b"] is None) or (a["norm"] is None and a["b"] is not None)
+                norm_ok = (a["norm"] in ("batch", "renorm") and not training and a["b"] is None) or (a["norm"] is None and a["b"] is not None)
                 if not norm_ok or a["act"] != "relu" or tuple(a["W"].shape[2:]) != (KF + Z if not units else 32, 32):
                     break
                 units.append(u)
@@ -387,7 +424,7 @@ class ForwardLowering:
         st_ptrs = []
         for u in rec["units"]:
             a = u.attrs
-            if a["norm"] == "batch":
+            if a["norm"] in ("batch", "renorm"):
                 nv = a["norm_vars"]
                 scale, shift = self._alloc((32,), F32), self._alloc((32,), F32)
                 self._bninfer_jobs.append((st.ptr(nv["gamma"]), st.ptr(nv["beta"]), st.ptr(nv["moving_mean"]), st.ptr(nv["moving_variance"]),
@@ -477,6 +514,8 @@ class ForwardLowering:
         nv = a["norm_vars"]
         o.params = (self.store.ptr(nv["gamma"]), self.store.ptr(nv["beta"]), tfnorm.EPS[sv.norm])
         o.moving = self._moving_args(nv, sv.norm == "batch" and o.training and self.loss is not None)
+        if sv.norm == "renorm":
+            self._renorm_setup(sv, nv, o.cout)
         sv.route, o.stats = conv_norm_route(self.L, sv.norm, o.training, bw, self.act_dt, o.x.dt, o.y.dt, o.out.dt, o.B, o.H, o.Wd, sv.cin_eff,
                                             o.cout, sv.G, sv.mfma, sv.head1x1, o.dual is not None, o.up is not None)
         getattr(self, "_fw_unit_" + sv.route.name.lower())(o, sv)
@@ -520,7 +559,8 @@ class ForwardLowering:
         # fp32 plans: the 3x3 convolution on the fp32 matrix instruction (same arithmetic class as the direct kernel: an fp32 FMA chain)
         f32m = bool(not mfma and self.act_dt == F32 and x.dt == F32 and out.dt == F32 and k == 3 and cout % 32 == 0 and _f32_mfma_enabled()
                     and isinstance(x, Buf) and self.L.conv3x3_f32_mfma_supported(B, H, Wd, cin, cout))
-        sv = ConvSaved(x, out, a["norm"], mfma, padded, cin_eff, bool(padded and k1), head1x1, f32m=f32m)
+        training = a["training"] if isinstance(a["training"], bool) else self.training
+        sv = ConvSaved(x, out, self._lowered_norm(a, training), mfma, padded, cin_eff, bool(padded and k1), head1x1, f32m=f32m)
         wptr, wf = self.store.ptr(W), None
         if padded:
             wf = self._alloc((9 * cin_eff * cout,), BF16)
@@ -530,7 +570,7 @@ class ForwardLowering:
             wf, _ = self._packed(W)
         return types.SimpleNamespace(op=op, a=a, bw=bw, sv=sv, x=x, out=out, W=W, k=k, cin=cin, cout=cout, B=B, H=H, Wd=Wd, dual=dual, up=up, xf=xf,
                                      wf=wf, wptr=wptr, bptr=self.store.ptr(b) if b is not None else None, act=rt.ACT_CODES[a["act"]],
-                                     training=a["training"] if isinstance(a["training"], bool) else self.training,
+                                     training=training,
                                      y=None, sums=None, pivot=None, stats=None, apply_args=None)
 
     def _mfma_conv(self, o, y, bias_p, oscale_p, act_code, stats, stats_mode, ws, wsb):
@@ -634,6 +674,18 @@ class ForwardLowering:
 
     _fw_unit_bn_small_f32y = _fw_unit_bn_small
 
+    def _fw_unit_renorm_small(self, o, sv):
+        # H <= 8 levels, training-mode batch renormalisation: the whole forward in one launch (phx_renorm_small_fwd); like batch norm the
+        # 2 x 2 / 4 x 4 levels of a bf16 plan keep the pre-normalisation tensor in fp32.  The backward pass is phx_bn_small_bwd's.
+        if (sv.mfma and not sv.head1x1 and _BN_SMALL_F32 and o.y.dt == BF16
+                and self.L.conv3x3_mfma_f32out_supported(o.B, o.H, o.Wd, sv.cin_eff, o.cout)):
+            self._conv_f32out(o, 1)
+        else:
+            self._conv_into(o, o.y, 0)
+        y, out, nv = o.y, o.out, o.a["norm_vars"]
+        self._emit(self.L.renorm_small_fwd, y.ptr, y.dt, *o.params, out.ptr, out.dt, sv.mean.ptr, sv.rstd.ptr, sv.scale.ptr, sv.shift.ptr,
+                   *self._renorm_args(sv, nv), sv.P, o.cout, o.act, self.stream, tag="bytes_norm_apply", flops=float(y.nbytes + out.nbytes))
+
     def _fw_unit_fgn(self, o, sv):
         # maps of at most 16 x 16: convolution, bias, group / instance norm and activation in ONE launch (a block holds whole
         # samples and whole groups: no cross-block step); the backward pass is phx_norm_small_bwd's
@@ -654,6 +706,8 @@ class ForwardLowering:
         """Statistics from o.stats (StatsSource), then the first apply-pass variant that takes the unit."""
         o.sums = self._alloc_zeroed(sv.NS * o.cout * 2)
         self._conv_with_stats(o, sv)
+        if sv.norm == "renorm":          # (no pool / head / depth-to-space / xf form: the plain renorm apply pass)
+            return self._renorm_apply(sv, o.a["norm_vars"], o.y, o.sums, o.pivot, o.out, o.cout, o.act)
         o.apply_args = self._norm_apply_args(sv, o.a, o.y, o.sums, o.pivot, o.out, o.cout, o.act, o.training)
         for apply in (self._apply_xf, self._apply_d2s, self._apply_head, self._apply_pool, self._apply_plain):
             if apply(o, sv):
@@ -798,8 +852,8 @@ class ForwardLowering:
         B, C = x.shape[0], x.shape[3]
         HW = x.shape[1] * x.shape[2]
         act = rt.ACT_CODES[a["act"]]
-        norm = a["norm"]
         training = a["training"] if isinstance(a["training"], bool) else self.training
+        norm = self._lowered_norm(a, training)
         sv = self.saved[op] = ConvSaved.plain(x, out, norm, C)
         if norm is None:
             ones = Buf((C,), F32, like=torch.ones(C, dtype=torch.float32, device=_device()))

@@ -89,7 +89,7 @@ def probunet_encoder_head(scope_name, rng_net, inputs, zdim_0, training, scope_r
     with g.variable_scope(scope_name) as scope:
         if scope_reuse:
             scope.reuse_variables()
-        add_bias = norm is not tfnorm.batch_norm
+        add_bias = norm not in (tfnorm.batch_norm, tfnorm.batch_renorm)
         enc = encoder(inputs, 'conv_%d_%d', widths, resolution_levels, norm, training, extra=dict(add_bias=add_bias))
         mu_p = layers.conv2D(enc[-1], 'pre_mu', num_filters=zdim_0, kernel_size=(1, 1), activation=act.identity)
         mu = [G.tile_batch(layers.global_averagepool2D(mu_p), tile)]

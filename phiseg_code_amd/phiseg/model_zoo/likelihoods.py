@@ -34,7 +34,7 @@ def det_unet2D(z_list, training, image_size, n_classes, scope_reuse=False, norm=
     with g.variable_scope('likelihood') as scope:
         if scope_reuse:
             scope.reuse_variables()
-        net, cu = _unet_on_x(x, widths, resolution_levels, norm, training, norm is not tfnorm.batch_norm)
+        net, cu = _unet_on_x(x, widths, resolution_levels, norm, training, norm not in (tfnorm.batch_norm, tfnorm.batch_renorm))
         for t in range(3):
             net = layers.conv2D(net, 'recomb_%d' % t, num_filters=widths[0], kernel_size=(1, 1), **cu)
         return [layers.conv2D(net, 'prediction', num_filters=n_classes, kernel_size=(1, 1), activation=act.identity)]
@@ -50,7 +50,7 @@ def prob_unet2D(z_list, training, image_size, n_classes, scope_reuse=False, norm
     with g.variable_scope('likelihood') as scope:
         if scope_reuse:
             scope.reuse_variables()
-        net, cu = _unet_on_x(x, widths, resolution_levels, norm, training, norm is not tfnorm.batch_norm)
+        net, cu = _unet_on_x(x, widths, resolution_levels, norm, training, norm not in (tfnorm.batch_norm, tfnorm.batch_renorm))
         if z.bmul > net.bmul:
             # n samples per image (priors.prob_unet2D with tile_samples=n): the U-Net ran once per image, its feature map is repeated
             # for the image's samples and only the recombination layers run at batch B * n

@@ -24,6 +24,7 @@ from phiseg_code_amd import engine
 from phiseg_code_amd import graph as G
 from phiseg_code_amd import optimizers
 from phiseg_code_amd import utils
+from phiseg_code_amd.tfwrapper import normalisation as tfnorm
 
 logging.basicConfig(level=logging.INFO, format='%(asctime)s %(message)s')
 
@@ -183,6 +184,9 @@ class phiseg():
         self.exp_config = exp_config
         self.bn_double_update = (os.environ.get("PHX_BN_DOUBLE_UPDATE", "0") == "1") if bn_double_update is None else bool(bn_double_update)
         self.init_seed = init_seed
+        if self.bn_double_update and exp_config.layer_norm is tfnorm.batch_renorm:
+            raise NotImplementedError("bn_double_update=True with layer_norm=batch_renorm: the two training-mode instances of a layer would "
+                                      "read and update the same renorm state within one step")
         self.checks()
         self.graph = G.reset_default_graph()
         L = exp_config.latent_levels
@@ -485,6 +489,10 @@ class phiseg():
         loss, hist, grids = self._summary_run(x_b, s_b, lr, histograms=True)
         spec = self._summary_spec()
         values = [S.scalar_value('batch_total_loss', loss), S.scalar_value('learning_rate', lr)]
+        if any(name.endswith('/renorm_mean') for name in self.graph.variables):
+            # normalisation.py:128-129: the clipping bounds of the batch-renorm layers -- the ones the training step `step` ran with
+            rmax, dmax = tfnorm.renorm_clip(step)
+            values += [S.scalar_value('rmax_clip', rmax), S.scalar_value('dmax_clip', dmax)]
         _, a_counts, a_stats = hist['act']
         for tag, t in spec['scalars']:
             st = a_stats[[i for i, u in enumerate(hist['seg_t']) if u is t][0]]
@@ -610,7 +618,8 @@ class phiseg():
         return out
 
     def _average_replica_state(self):
-        """Data parallel: batch-norm moving statistics are per replica; average them over the ranks."""
+        """Data parallel: batch-norm moving statistics are per replica; average them over the ranks.  The whole
+        state arena is averaged: a batch-renorm layer's renorm_mean / renorm_stddev with it (its two weights are equal on all ranks)."""
         store = self.sess._ensure_store()
         if self.dist is not None and self.dist.active and store.n_state:
             avg = store.state.clone()

@@ -85,7 +85,8 @@ class _Lib:
             if name in ("phx_abi_version", "phx_last_error", "phx_bn_small_supported", "phx_bn_wide_supported", "phx_norm_apply_pool_supported", "phx_upconv_supported", "phx_norm_small_supported", "phx_norm_head_supported", "phx_conv3x3_wgrad_xf_supported", "phx_conv3x3_wgrad_multi_job_bytes", "phx_conv3x3_wgrad_ws_bytes", "phx_conv3x3_wgrad_ws_bytes_dual", "phx_augment_param_bytes", "phx_augment_batch_elastic_ws_bytes",
                         "phx_conv3x3_desc_bytes", "phx_validation_metrics_ws_bytes", "phx_eval_metrics_ws_bytes", "phx_mc_stats_ws_bytes", "phx_summary_histograms_ws_bytes", "phx_conv2d_direct_wgrad_ordered_ws_bytes", "phx_dice_ws_bytes", "phx_seg_xent_ws_bytes",
                         "phx_conv3x3_f32_mfma_supported", "phx_conv3x3_f32_mfma_packed_floats", "phx_conv3x3_f32_mfma_wgrad_supported",
-                        "phx_conv3x3_f32_mfma_wgrad_ws_bytes", "phx_bn_bwd_onepass_supported", "phx_bn_bwd_onepass_barrier_words"):
+                        "phx_conv3x3_f32_mfma_wgrad_ws_bytes", "phx_bn_bwd_onepass_supported", "phx_bn_bwd_onepass_barrier_words",
+                        "phx_renorm_small_supported", "phx_renorm_tail_desc_bytes"):
                 if name.endswith("_ws_bytes") or name.endswith("_packed_floats"):
                     fn.restype = ctypes.c_size_t
                 setattr(self, name[4:], fn)

@@ -68,7 +68,9 @@ def conv2D(x,
     with g.variable_scope(name):
         weights = utils.get_weight_variable(weight_shape, name='W', type=weight_init, regularize=True)
         biases = None
-        if add_bias and normalisation is tfnorm.batch_norm:
+        if add_bias and normalisation in (tfnorm.batch_norm, tfnorm.batch_renorm):
+            # (batch_renorm: the reference keeps the bias there; with r and d constant for the gradient it gets none and stays at its
+            # zero initial value, so leaving it out changes no result -- DESIGN.md section 7f)
             logging.debug('Turning of bias because using batch norm.')
             add_bias = False
         if add_bias:

@@ -42,18 +42,39 @@ def layer_norm(x, **kwargs):
     raise NotImplementedError("layer_norm has no call site in phiseg/ (out of scope, SURVEY.md section 2)")
 
 
-def batch_renorm(x, **kwargs):
-    raise NotImplementedError("batch_renorm has no call site in phiseg/ (out of scope, SURVEY.md section 2)")
+def batch_renorm(x, training=None, moving_average_decay=0.99, scope="batch_renorm", **kwargs):
+    """tf.contrib.layers.batch_norm(renorm=True, renorm_decay=.99, epsilon=1e-3, center, scale, renorm_clipping={rmax, dmax}) with the
+    clipping schedule of renorm_clip -- normalisation.py:72-142 (the formulae: DESIGN.md section 7f)."""
+    return _standalone("batch_renorm")(x)
 
 
-KIND = {batch_norm: "batch", group_norm2D: "group", instance_norm2D: "instance", identity: None}
-EPS = {"batch": 1e-3, "group": 1e-5, "instance": 1e-5}
+KIND = {batch_norm: "batch", group_norm2D: "group", instance_norm2D: "instance", identity: None, batch_renorm: "renorm"}
+EPS = {"batch": 1e-3, "group": 1e-5, "instance": 1e-5, "renorm": 1e-3}
 BN_DECAY = 0.99
+RENORM_DECAY = 0.99                 # renorm_decay (the reference's moving_average_decay goes here)
+RENORM_MOVING_DECAY = 0.999         # contrib's default `decay`, which the reference leaves alone: the moving statistics' decay
+RENORM_STATE = ("renorm_mean", "renorm_mean_weight", "renorm_stddev", "renorm_stddev_weight")
+
+
+def renorm_clip(step):
+    """Host mirror of the clipping schedule the renorm kernels evaluate on the device (normalisation.py:82-126; fp32 like
+    tf.to_float(global_step)) -> (rmax, dmax) at optimiser step `step`: rmax is 1 up to step 500 and 3 beyond 4000, dmax 0 up to 500
+    and 5 beyond 2500, both linear in between."""
+    x = np.float32(int(step))
+    lo, f = np.float32(500.0), np.float32
+
+    def ramp(y_min, y_max, x_max):
+        if x < lo:
+            return f(y_min)
+        if x > f(x_max):
+            return f(y_max)
+        return f(f(f(x - lo) * f(y_max - y_min)) / f(x_max - 500.0)) + f(y_min)
+    return float(ramp(1.0, 3.0, 4000.0)), float(ramp(0.0, 5.0, 2500.0))
 
 
 def make_variables(kind, channels, scope=None):
     """Create the norm's variables inside the CURRENT scope (the conv's name scope); `scope` replaces the callable's default
-    scope name (batch_norm / group_norm / instance_norm), as the residual units pass scope='bn1' (layers.py:452-456)."""
+    scope name (batch_norm / batch_renorm / group_norm / instance_norm), as the residual units pass scope='bn1' (layers.py:452-456)."""
     g = G.get_default_graph()
     if kind == "batch":
         with g.variable_scope(scope or "batch_norm"):
@@ -62,6 +83,17 @@ def make_variables(kind, channels, scope=None):
                             gamma=g.get_variable("gamma", [channels], _ones),
                             moving_mean=g.get_variable("moving_mean", [channels], _zeros, trainable=False),
                             moving_variance=g.get_variable("moving_variance", [channels], _ones, trainable=False))
+    if kind == "renorm":
+        # the four batch-norm variables, then TF's renorm variables in its creation order; the two weights are scalars (shape ())
+        with g.variable_scope(scope or "batch_renorm"):
+            with g.variable_scope("BatchNorm"):
+                nv = dict(beta=g.get_variable("beta", [channels], _zeros),
+                          gamma=g.get_variable("gamma", [channels], _ones),
+                          moving_mean=g.get_variable("moving_mean", [channels], _zeros, trainable=False),
+                          moving_variance=g.get_variable("moving_variance", [channels], _ones, trainable=False))
+                for name in RENORM_STATE:
+                    nv[name] = g.get_variable(name, [] if name.endswith("_weight") else [channels], _zeros, trainable=False)
+                return nv
     if kind == "group":
         with g.variable_scope(scope or "group_norm"):
             return dict(gamma=g.get_variable("gamma", [1, 1, 1, channels], _ones),
