@@ -551,7 +551,8 @@ int phx_philox_normal(float* out, int B, int per_sample, uint64_t seed, const in
 /* residual multinoulli loss over L levels: logits s[l] are [B, H>>shift[l], W>>shift[l], C] fp32 (the
  * NEAREST_NEIGHBOR resize of likelihoods.py:221 is folded into the read).  losses[l] = inv_batch * sum CE_l
  * (written; `losses` must hold 8 + 512 floats, the tail is scratch for the partial sums; nullable).
- * ds[l] (nullable; level 0 is written, coarser levels must be zeroed) += weight*inv_batch * d(sum_l CE_l)/d s[l].
+ * ds[l] (nullable) = weight*inv_batch * d(sum_l CE_l)/d s[l]: every level is WRITTEN with plain stores (each element has
+ * one writer), nothing is accumulated and the caller need not initialise ds.
  * labels may be NULL when only s_out (= sum_l s[l] at full resolution, nullable) / sm_out (= softmax(s_out),
  * nullable) are wanted (sampling path, phiseg_model.py:106-109). */
 int phx_residual_ce(const float* const* s, float* const* ds, const int* shift, int L, const uint8_t* labels,
