@@ -2,6 +2,7 @@
 // scale / shift, affine + activation, and the fused apply passes (plain, with a 1x1 head, depth-to-space, with the 2 x 2 average pool).
 // The backward passes: norm_bwd.hip; the one-launch layers of the small maps: norm_onelaunch.hip.
 #include <stdlib.h>
+#include <type_traits>
 
 #include "norm_common.h"
 
@@ -231,53 +232,85 @@ struct HeadFw {
     int ph, pw;          // > 0: x is in the packed pixel order of the phase-form convolution (csrc/upconv.hip: [B][ph][pw][(a, b)] pixels), y is
                          // written as the hi-res map [B][2 ph][2 pw] -- the depth-to-space permutation rides on the apply pass
 };
-template <typename TI, typename TO, int V, int HN = 0>
-__global__ void k_norm_apply_fused(const TI* __restrict__ x, const float* __restrict__ sums,
-                                   const float* __restrict__ pivot, const float* __restrict__ gamma,
-                                   const float* __restrict__ beta, float eps, TO* __restrict__ y, float* mean_out,
-                                   float* rstd_out, float* scale_out, float* shift_out, float* moving_mean,
-                                   float* moving_var, float momentum, int P, int C, int G, int PL, int chunk, int act, int nrep,
-                                   HeadFw hd) {
-    const int CV = C / V, cg = C / G;
-    const int ns = blockIdx.y;
-    const int cv = threadIdx.x % CV, pl = threadIdx.x / CV;
-    // The statistics are finalised ONCE per block, cooperatively, into LDS: thread g derives (mean, rstd) of statistic g, thread c
-    // the (scale, shift) of channel c.  (Every thread deriving the eight channels it streams -- 30-50 loads of the same few cache
-    // lines per thread -- made the prologue 4-5 us per block and a launch with many blocks a hot spot in one L2 channel: these
-    // kernels ran at 2.4-4.7 TB/s where a plain copy of the same tensor reaches 6-7.)
-    extern __shared__ float lds_f[];
-    float* gst = lds_f;                          // [G][2]  mean, rstd
-    float* cof = lds_f + 2 * G;                  // [C][2]  scale, shift
+// The statistics of sample group blockIdx.y finalised ONCE per block, cooperatively, into LDS: gst[G][2] = mean, rstd, cof[C][2] = scale,
+// shift; block (0, ns) publishes them and does the moving update.  (Every thread deriving the eight channels it streams -- 30-50 loads
+// of the same few cache lines per thread -- made the prologue 4-5 us per block and a launch with many blocks a hot spot in one L2
+// channel: these kernels ran at 2.4-4.7 TB/s where a plain copy of the same tensor reaches 6-7.)
+// In two parts, so that a kernel can put its first data loads between them: norm_apply_loads issues what this thread's first channel
+// needs (sums, pivot, gamma, beta -- loads return in issue order, so issued first they are waited for alone; a thread past C loads
+// channel C - 1 and discards it: no branch), norm_apply_prologue derives the coefficients and ends with the block's barrier.
+struct NormChanLoads {
+    float2 sq;           // {sum, sum of squares} (pivot-shifted), replica 0
+    float pv, gm, bt;
+};
+__device__ __forceinline__ NormChanLoads norm_apply_loads(const float* __restrict__ sums, const float* __restrict__ pivot,
+                                                          const float* __restrict__ gamma, const float* __restrict__ beta, int C, int c) {
+    NormChanLoads k;
+    const size_t nc = (size_t)blockIdx.y * C + c;
+    k.sq = *reinterpret_cast<const float2*>(sums + nc * 2);
+    k.pv = pivot ? pivot[nc] : 0.f;
+    k.gm = gamma[c];
+    k.bt = beta[c];
+    return k;
+}
+__device__ __forceinline__ void norm_apply_prologue(const NormChanLoads& k0, const float* __restrict__ sums, const float* __restrict__ pivot,
+                                                    const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                    float* mean_out, float* rstd_out, float* scale_out, float* shift_out,
+                                                    float* moving_mean, float* moving_var, float momentum, int P, int C, int G, int nrep,
+                                                    float* gst, float* cof) {
+    const int cg = C / G, ns = blockIdx.y;
     const float invP = 1.f / (float)P;
     const bool pub = blockIdx.x == 0;
-    for (int g = threadIdx.x; g < G; g += blockDim.x) {
-        float mu, var;
-        if (cg == 1) {                                      // batch / instance norm: one channel per statistic
-            float2 sq = *reinterpret_cast<const float2*>(sums + ((size_t)ns * C + g) * 2);
+    if (cg == 1) {
+        // batch / instance norm, one channel per statistic: thread c has issued everything channel c needs together and derives
+        // mean / rstd / scale / shift on its own -- one memory round trip and one barrier
+        for (int c = threadIdx.x; c < C; c += blockDim.x) {
+            const size_t nc = (size_t)ns * C + c;
+            NormChanLoads k = k0;
+            if (c != (int)threadIdx.x) k = norm_apply_loads(sums, pivot, gamma, beta, C, c);      // (C > 256 only)
+            float2 sq = k.sq;
             for (int r = 1; r < nrep; ++r) {                    // (replicated accumulators: nrep is 1 on every shipped path)
-                const float2 q = *reinterpret_cast<const float2*>(sums + (((size_t)r * gridDim.y + ns) * C + g) * 2);
+                const float2 q = *reinterpret_cast<const float2*>(sums + (((size_t)r * gridDim.y + ns) * C + c) * 2);
                 sq.x += q.x; sq.y += q.y;
             }
-            float rs1;
-            chan_coeffs(sq.x, sq.y, pivot ? pivot[(size_t)ns * C + g] : 0.f, invP, eps, &mu, &var, &rs1);
-        } else {
-            group_stats(sums, pivot, ns, C, g, cg, invP, eps, &mu, &var);
+            float mu, var, rs1, scv, shv;
+            chan_coeffs(sq.x, sq.y, k.pv, invP, eps, &mu, &var, &rs1);
+            const float rs = rsqrtf(var + eps);
+            chan_scale_shift(k.gm, k.bt, mu, rs, &scv, &shv);
+            cof[2 * c] = scv;
+            cof[2 * c + 1] = shv;
+            if (pub) {
+                mean_out[nc] = mu;
+                rstd_out[nc] = rs;
+                if (momentum > 0.f && moving_mean)            // batch norm (G == C): TF1 fused-batch-norm moving update
+                    moving_update(&moving_mean[c], &moving_var[c], mu, var, (float)P * (float)cg, momentum);
+                scale_out[nc] = scv;
+                shift_out[nc] = shv;
+            }
         }
+        __syncthreads();
+        return;
+    }
+    // group norm: thread g derives (mean, rstd) of statistic g, thread c the (scale, shift) of channel c (its first channel's gamma /
+    // beta are there already)
+    for (int g = threadIdx.x; g < G; g += blockDim.x) {
+        float mu, var;
+        group_stats(sums, pivot, ns, C, g, cg, invP, eps, &mu, &var);
         const float rs = rsqrtf(var + eps);
         gst[2 * g] = mu;
         gst[2 * g + 1] = rs;
         if (pub) {
             mean_out[ns * G + g] = mu;
             rstd_out[ns * G + g] = rs;
-            if (momentum > 0.f && moving_mean)            // batch norm (G == C): TF1 fused-batch-norm moving update
-                moving_update(&moving_mean[g], &moving_var[g], mu, var, (float)P * (float)cg, momentum);
+            if (momentum > 0.f && moving_mean) moving_update(&moving_mean[g], &moving_var[g], mu, var, (float)P * (float)cg, momentum);
         }
     }
     __syncthreads();
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
         const int g = c / cg;
+        const bool first = c == (int)threadIdx.x;
         float scv, shv;
-        chan_scale_shift(gamma[c], beta[c], gst[2 * g], gst[2 * g + 1], &scv, &shv);
+        chan_scale_shift(first ? k0.gm : gamma[c], first ? k0.bt : beta[c], gst[2 * g], gst[2 * g + 1], &scv, &shv);
         cof[2 * c] = scv;
         cof[2 * c + 1] = shv;
         if (pub) {
@@ -286,20 +319,49 @@ __global__ void k_norm_apply_fused(const TI* __restrict__ x, const float* __rest
         }
     }
     __syncthreads();
+}
+
+template <typename TI, typename TO, int V, int HN = 0>
+__global__ void k_norm_apply_fused(const TI* __restrict__ x, const float* __restrict__ sums,
+                                   const float* __restrict__ pivot, const float* __restrict__ gamma,
+                                   const float* __restrict__ beta, float eps, TO* __restrict__ y, float* mean_out,
+                                   float* rstd_out, float* scale_out, float* shift_out, float* moving_mean,
+                                   float* moving_var, float momentum, int P, int C, int G, int PL, int chunk, int act, int nrep,
+                                   HeadFw hd) {
+    const int CV = C / V;
+    const int ns = blockIdx.y;
+    const int cv = threadIdx.x % CV, pl = threadIdx.x / CV;
+    extern __shared__ float lds_f[];
+    float* gst = lds_f;                          // [G][2]  mean, rstd
+    float* cof = lds_f + 2 * G;                  // [C][2]  scale, shift
+    const int p0 = blockIdx.x * chunk, p1 = min(P, p0 + chunk);
+    // EARLY (bf16 input, 16-byte vectors): the first trip's loads are issued ahead of the finalisation and held packed until the
+    // coefficients are there -- the streamed data depend on nothing, and a block's first loads miss L2 (the producer ran on another
+    // XCD), so behind the prologue they were a round trip of their own.  Pixels past the block's range are clamped to its last pixel
+    // (a valid address: no block has an empty range, see the launcher) and their values discarded.
+    constexpr bool EARLY = V == 8 && std::is_same<TI, bf16_t>::value;
+    const NormChanLoads k0 = norm_apply_loads(sums, pivot, gamma, beta, C, min((int)threadIdx.x, C - 1));
+    uint4 xe[EARLY ? 4 : 1];
+    if constexpr (EARLY) {                       // (no branch around the loads: a merge would wait for them)
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            xe[u] = *reinterpret_cast<const uint4*>(x + ((size_t)ns * P + min(p0 + pl + u * PL, p1 - 1)) * C + (size_t)cv * V);
+    }
+    float hw[V][HN > 0 ? HN : 1];
+    if constexpr (HN > 0) {                      // (the head's filter rows: independent loads, out with the first trip's)
+#pragma unroll
+        for (int j = 0; j < V; ++j)
+#pragma unroll
+            for (int o = 0; o < HN; ++o) hw[j][o] = hd.w[(size_t)(cv * V + j) * HN + o];
+    }
+    norm_apply_prologue(k0, sums, pivot, gamma, beta, eps, mean_out, rstd_out, scale_out, shift_out, moving_mean, moving_var, momentum, P, C,
+                        G, nrep, gst, cof);
     if (pl >= PL) return;
     float sc[V], sh[V];
 #pragma unroll
     for (int j = 0; j < V; ++j) {
         sc[j] = cof[2 * (cv * V + j)];
         sh[j] = cof[2 * (cv * V + j) + 1];
-    }
-    const int p0 = blockIdx.x * chunk, p1 = min(P, p0 + chunk);
-    float hw[V][HN > 0 ? HN : 1];
-    if constexpr (HN > 0) {
-#pragma unroll
-        for (int j = 0; j < V; ++j)
-#pragma unroll
-            for (int o = 0; o < HN; ++o) hw[j][o] = hd.w[(size_t)(cv * V + j) * HN + o];
     }
     auto head = [&](size_t pix, const float (&a)[V]) {     // (all CV lanes of the pixel are active together)
         if constexpr (HN > 0) {
@@ -323,6 +385,20 @@ __global__ void k_norm_apply_fused(const TI* __restrict__ x, const float* __rest
     };
     auto yoff = [&](size_t pix) -> size_t { return (hd.pw > 0 ? packed_to_hi_pixel(pix, hd.ph, hd.pw) : pix) * C + (size_t)cv * V; };
     int p = p0 + pl;
+    if constexpr (EARLY) {                       // the first four pixels: loaded ahead of the prologue
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (p + u * PL < p1) {
+                float v[V];
+                bf16x8_unpack(xe[u], v);
+#pragma unroll
+                for (int j = 0; j < V; ++j) v[j] = act_fwd(fmaf(v[j], sc[j], sh[j]), act);
+                if (HN == 0 || y != nullptr) VecIO<TO, V>::store(y, yoff((size_t)ns * P + p + u * PL), v);
+                head((size_t)ns * P + p + u * PL, v);
+            }
+        }
+        p += 4 * PL;
+    }
     for (; p + 3 * PL < p1; p += 4 * PL) {       // four pixels per trip, loads first (see k_norm_stats)
         float v[4][V];
 #pragma unroll
@@ -359,45 +435,25 @@ __global__ void k_norm_apply_pool(const bf16_t* __restrict__ x, const float* __r
                                   float* moving_mean, float* moving_var, float momentum, int P, int C, int G, int H, int W, int PL,
                                   int chunk, int act) {
     constexpr int V = 8;
-    const int CV = C / V, cg = C / G;
+    const int CV = C / V;
     const int ns = blockIdx.y;
     const int cv = threadIdx.x % CV, pl = threadIdx.x / CV;
     extern __shared__ float lds_f[];
     float* gst = lds_f;                          // [G][2]  mean, rstd
     float* cof = lds_f + 2 * G;                  // [C][2]  scale, shift
-    const float invP = 1.f / (float)P;
-    const bool pub = blockIdx.x == 0;
-    for (int g = threadIdx.x; g < G; g += blockDim.x) {
-        float mu, var;
-        if (cg == 1) {
-            const float2 sq = *reinterpret_cast<const float2*>(sums + ((size_t)ns * C + g) * 2);
-            float rs1;
-            chan_coeffs(sq.x, sq.y, pivot ? pivot[(size_t)ns * C + g] : 0.f, invP, eps, &mu, &var, &rs1);
-        } else {
-            group_stats(sums, pivot, ns, C, g, cg, invP, eps, &mu, &var);
-        }
-        const float rs = rsqrtf(var + eps);
-        gst[2 * g] = mu;
-        gst[2 * g + 1] = rs;
-        if (pub) {
-            mean_out[ns * G + g] = mu;
-            rstd_out[ns * G + g] = rs;
-            if (momentum > 0.f && moving_mean) moving_update(&moving_mean[g], &moving_var[g], mu, var, (float)P * (float)cg, momentum);
-        }
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        const int g = c / cg;
-        float scv, shv;
-        chan_scale_shift(gamma[c], beta[c], gst[2 * g], gst[2 * g + 1], &scv, &shv);
-        cof[2 * c] = scv;
-        cof[2 * c + 1] = shv;
-        if (pub) {
-            scale_out[(size_t)ns * C + c] = scv;
-            shift_out[(size_t)ns * C + c] = shv;
-        }
-    }
-    __syncthreads();
+    const int Hh = H >> 1, Wh = W >> 1, Q = P >> 2;               // quads of this sample group (P = images x H x W)
+    const int q0 = blockIdx.x * chunk, q1 = min(Q, q0 + chunk);
+    auto quad_pixels = [&](int q, size_t (&off)[4]) {             // k_avgpool_fwd's order: (0,0), (0,1), (1,0), (1,1)
+        const int bl = q / (Hh * Wh), r = q - bl * (Hh * Wh);
+        const int yq = r / Wh, xq = r - yq * Wh;
+        const size_t p00 = (size_t)ns * P + ((size_t)bl * H + 2 * yq) * W + 2 * xq;
+        off[0] = p00; off[1] = p00 + 1; off[2] = p00 + W; off[3] = p00 + W + 1;
+    };
+    // (the first quad's loads stay behind the finalisation here: held packed across it they cost the kernel a wave per SIMD -- 74
+    // registers against 72 -- and these kernels lose more from occupancy than from a round trip)
+    const NormChanLoads k0 = norm_apply_loads(sums, pivot, gamma, beta, C, min((int)threadIdx.x, C - 1));
+    norm_apply_prologue(k0, sums, pivot, gamma, beta, eps, mean_out, rstd_out, scale_out, shift_out, moving_mean, moving_var, momentum, P, C,
+                        G, 1, gst, cof);
     if (pl >= PL) return;
     float sc[V], sh[V];
 #pragma unroll
@@ -405,13 +461,9 @@ __global__ void k_norm_apply_pool(const bf16_t* __restrict__ x, const float* __r
         sc[j] = cof[2 * (cv * V + j)];
         sh[j] = cof[2 * (cv * V + j) + 1];
     }
-    const int Hh = H >> 1, Wh = W >> 1, Q = P >> 2;               // quads of this sample group (P = images x H x W)
-    const int q0 = blockIdx.x * chunk, q1 = min(Q, q0 + chunk);
     for (int q = q0 + pl; q < q1; q += PL) {
-        const int bl = q / (Hh * Wh), r = q - bl * (Hh * Wh);
-        const int yq = r / Wh, xq = r - yq * Wh;
-        const size_t p00 = (size_t)ns * P + ((size_t)bl * H + 2 * yq) * W + 2 * xq;
-        const size_t off[4] = {p00, p00 + 1, p00 + W, p00 + W + 1};      // k_avgpool_fwd's order: (0,0), (0,1), (1,0), (1,1)
+        size_t off[4];
+        quad_pixels(q, off);
         float v[4][V];
 #pragma unroll
         for (int u = 0; u < 4; ++u) VecIO<bf16_t, V>::load(x, off[u] * C + (size_t)cv * V, v[u]);
@@ -519,6 +571,7 @@ static int norm_apply_impl(const void* x, int x_dt, const float* sums, int nrep,
 #define NA_LAUNCH(TI, TO, Vv, HNv)                                                                                                \
     do {                                                                                                                          \
         PHX_REQUIRE(too_large == 0, PHX_E_SHAPE, hn > 0 ? "norm_apply_fused_head: C too large" : "norm_apply_fused: C too large"); \
+        PHX_REQUIRE(block_ranges_nonempty(P, chunk, nchunks), PHX_E_SHAPE, "norm_apply_fused: a block without pixels");           \
         hipLaunchKernelGGL((k_norm_apply_fused<TI, TO, Vv, HNv>), dim3(nchunks, NS), dim3(threads), (size_t)2 * (C + G) * sizeof(float), \
                            (hipStream_t)stream, (const TI*)x, sums, pivot, gamma, beta, eps, (TO*)y, mean, rstd, scale, shift,     \
                            moving_mean, moving_var, momentum, P, C, G, PL, chunk, act, nrep, hd);                                 \
@@ -553,8 +606,7 @@ int phx_norm_apply_pool(const void* x, const float* sums, const float* pivot, co
     PHX_REQUIRE(x && y && y_pool && sums, PHX_E_INVAL, "norm_apply_pool: null argument");
     PHX_REQUIRE(momentum == 0.f || (NS == 1 && G == C), PHX_E_INVAL, "moving update only for batch norm");
     int PL, threads, chunk, nchunks;
-    PHX_REQUIRE(stream_geometry(P / 4, C, 8, &PL, &threads, &chunk, &nchunks, NS) == 0, PHX_E_SHAPE, "norm_apply_pool: C too large");
-    hipLaunchKernelGGL(k_norm_apply_pool, dim3(nchunks, NS), dim3(threads), (size_t)2 * (C + G) * sizeof(float), (hipStream_t)stream,
+    PHX_REQUIRE(stream_geometry(P / 4, C, 8, &PL, &threads, &chunk, &nchunks, NS) == 0, PHX_E_SHAPE, "norm_apply_pool: C too large");    hipLaunchKernelGGL(k_norm_apply_pool, dim3(nchunks, NS), dim3(threads), (size_t)2 * (C + G) * sizeof(float), (hipStream_t)stream,
                        (const bf16_t*)x, sums, pivot, gamma, beta, eps, (bf16_t*)y, (bf16_t*)y_pool, mean, rstd, scale, shift, moving_mean,
                        moving_var, momentum, P, C, G, H, W, PL, chunk, act);
     PHX_CHECK_LAUNCH();

@@ -86,6 +86,11 @@ __device__ __forceinline__ void head_rider_fma(const float (&xv)[V], const float
     }
 }
 
+// what k_norm_bwd_apply_fused's one-stage finalisation reads for one channel
+struct BwdChanLoads {
+    float gm, rs, mu, sc, sh, fs, fp;
+    float2 v[4];         // {sum g, sum g * xhat} of four accumulator replicas
+};
 template <typename TD, typename TX, typename TO, int V, int HN = 0>
 __global__ void k_norm_bwd_apply_fused(const TD* __restrict__ dA, const TX* __restrict__ x,
                                        const float* __restrict__ scale, const float* __restrict__ shift,
@@ -112,48 +117,115 @@ __global__ void k_norm_bwd_apply_fused(const TD* __restrict__ dA, const TX* __re
     extern __shared__ float st[];
     float* sg = st + 2 * C;
     float* cof = sg + 2 * G;
-    {
-        const size_t rstride = (size_t)gridDim.y * 2 * C;    // sums2[nrep][NS][C][2]
+    // EARLY (bf16 tensors, 16-byte vectors, dA a tensor): the first trip's (x, dA) loads are issued ahead of the finalisation and held
+    // packed until the coefficients are there -- the streamed data depend on nothing.  Pixels past the block's range are clamped to its
+    // last pixel (a valid address: no block has an empty range, see the launcher) and their values discarded.
+    constexpr bool EARLY = V == 8 && HN == 0 && std::is_same<TD, bf16_t>::value && std::is_same<TX, bf16_t>::value;
+    // (the fp32 instantiations keep the three-stage finalisation for every G: with the one-stage form they spill more)
+    constexpr bool ONE_STAGE = std::is_same<TD, bf16_t>::value && std::is_same<TX, bf16_t>::value;
+    const int p0 = blockIdx.x * chunk, p1 = min(P, p0 + chunk);
+    const size_t rstride = (size_t)gridDim.y * 2 * C;        // sums2[nrep][NS][C][2]
+    // everything the one-stage finalisation reads for channel c, issued together (fs, fp: the bias form, block 0 only)
+    auto load4 = [&](int c, int r0, float2 (&v)[4]) {         // replicas r0 .. r0 + 3 (clamped to the last: always a valid address)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const float2*>(sums2 + min(r0 + q, nrep - 1) * rstride + ((size_t)ns * C + c) * 2);
+    };
+    auto chan_loads = [&](int c) {
+        BwdChanLoads k;
+        const size_t nc = (size_t)ns * C + c;
+        k.gm = gamma[c]; k.rs = rstd[nc]; k.mu = mean[nc]; k.sc = scale[nc]; k.sh = shift[nc];
+        const bool bias = blockIdx.x == 0 && dbias;
+        k.fs = bias ? fsums[nc * 2] : 0.f;
+        k.fp = bias && fpivot ? fpivot[nc] : 0.f;
+        load4(c, 0, k.v);
+        return k;
+    };
+    // The loads of this thread's first channel go out AHEAD of the data loads: loads return in issue order, so the finalisation waits
+    // for them alone and runs while the data are still in flight.  (A thread past C loads channel C - 1 and discards it: no branch.)
+    BwdChanLoads k0 = {};
+    if (ONE_STAGE && cg == 1) k0 = chan_loads(min((int)threadIdx.x, C - 1));
+    uint4 xe[EARLY ? 4 : 1], de[EARLY ? 4 : 1];
+    if constexpr (EARLY) {                       // (no branch around the loads: a merge would wait for them)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const size_t pix = (size_t)ns * P + min(p0 + pl + u * PL, p1 - 1);
+            const size_t off = pix * C + (size_t)cv * V;
+            xe[u] = *reinterpret_cast<const uint4*>(x + off);
+            de[u] = *reinterpret_cast<const uint4*>(dA + (hb.pw > 0 ? packed_to_hi_pixel(pix, hb.ph, hb.pw) * hb.pc + (size_t)cv * V : off));
+        }
+    }
+    const float inv_m = 1.f / ((float)P * (float)cg);
+    // the bias form's closed-form sum (block 0 only), from loads already in registers
+    auto publish = [&](int c, float t0, float t1, float ca, float cc, float rs, float mu, float S0, float fs, float fp) {
+        atomicAdd(&dbeta[c], t0);
+        atomicAdd(&dgamma[c], t1);
+        if (dbias) {
+            // gradient of the bias the producing convolution adds BEFORE the normalisation (group / instance norm keep it,
+            // layers.py:126-132): sum_p dx[ns, p, c] = a * sum g + P * b + c * sum x, in closed form from the per-channel
+            // sums of both passes -- no pass over dx.  (sum x - P * mean from the shifted forward sums: no cancellation.)
+            const float dsum = fs + (float)P * (fp - mu);
+            atomicAdd(&dbias[c], fmaf(ca, t0, fmaf(cc, dsum, -(float)P * rs * S0 * inv_m)));
+        }
+    };
+    if (ONE_STAGE && cg == 1) {
+        // batch / instance norm, one channel per statistic: S0, S1 are gamma * st of the SAME channel, so thread c takes channel c from
+        // the accumulator replicas to the coefficients on its own -- every per-channel load issued together, one LDS stage, one barrier
+        for (int c = threadIdx.x; c < C; c += blockDim.x) {
+            const bool first = c == (int)threadIdx.x;        // this thread's first channel: loaded ahead of the data, above
+            BwdChanLoads k = k0;
+            if (!first) k = chan_loads(c);
+            const float gm = k.gm, rs = k.rs, mu = k.mu, scv = k.sc, shv = k.sh, fs = k.fs, fp = k.fp;
+            float t0 = 0.f, t1 = 0.f;
+            for (int r0 = 0; r0 < nrep; r0 += 4) {           // four replicas in flight, added in replica order
+                if (r0 > 0) load4(c, r0, k.v);
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (r0 + q < nrep) { t0 += k.v[q].x; t1 += k.v[q].y; }
+            }
+            float S0 = 0.f, S1 = 0.f;
+            S0 += gm * t0;
+            S1 += gm * t1;
+            const float ca = rs * gm;
+            const float cc = -rs * rs * S1 * inv_m;
+            cof[5 * c] = ca;
+            cof[5 * c + 1] = -rs * S0 * inv_m - cc * mu;
+            cof[5 * c + 2] = cc;
+            cof[5 * c + 3] = scv;
+            cof[5 * c + 4] = shv;
+            if (blockIdx.x == 0) publish(c, t0, t1, ca, cc, rs, mu, S0, fs, fp);
+        }
+    } else {
+        // group norm: the statistic's sums cross channels -- three stages (replica sums, per-group S0 / S1, coefficients)
         for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {
             float a = 0.f;
             for (int r = 0; r < nrep; ++r) a += sums2[r * rstride + (size_t)ns * 2 * C + i];
             st[i] = a;
         }
-    }
-    __syncthreads();
-    for (int g = threadIdx.x; g < G; g += blockDim.x) {
-        float S0 = 0.f, S1 = 0.f;
-        for (int q = g * cg; q < (g + 1) * cg; ++q) {
-            const float gm = gamma[q];
-            S0 += gm * st[2 * q];
-            S1 += gm * st[2 * q + 1];
-        }
-        sg[2 * g] = S0;
-        sg[2 * g + 1] = S1;
-    }
-    __syncthreads();
-    const float inv_m = 1.f / ((float)P * (float)cg);
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        const int g = c / cg, sgi = ns * G + g;
-        const float rs = rstd[sgi], mu = mean[sgi], S0 = sg[2 * g], S1 = sg[2 * g + 1];
-        const float ca = rs * gamma[c];
-        const float cc = -rs * rs * S1 * inv_m;
-        cof[5 * c] = ca;
-        cof[5 * c + 1] = -rs * S0 * inv_m - cc * mu;
-        cof[5 * c + 2] = cc;
-        cof[5 * c + 3] = scale[(size_t)ns * C + c];
-        cof[5 * c + 4] = shift[(size_t)ns * C + c];
-        if (blockIdx.x == 0) {
-            const float t0 = st[2 * c], t1 = st[2 * c + 1];      // this channel's {sum g, sum g * xhat}
-            atomicAdd(&dbeta[c], t0);
-            atomicAdd(&dgamma[c], t1);
-            if (dbias) {
-                // gradient of the bias the producing convolution adds BEFORE the normalisation (group / instance norm keep it,
-                // layers.py:126-132): sum_p dx[ns, p, c] = a * sum g + P * b + c * sum x, in closed form from the per-channel
-                // sums of both passes -- no pass over dx.  (sum x - P * mean from the shifted forward sums: no cancellation.)
-                const float dsum = fsums[((size_t)ns * C + c) * 2] + (float)P * ((fpivot ? fpivot[(size_t)ns * C + c] : 0.f) - mu);
-                atomicAdd(&dbias[c], fmaf(ca, t0, fmaf(cc, dsum, -(float)P * rs * S0 * inv_m)));
+        __syncthreads();
+        for (int g = threadIdx.x; g < G; g += blockDim.x) {
+            float S0 = 0.f, S1 = 0.f;
+            for (int q = g * cg; q < (g + 1) * cg; ++q) {
+                const float gm = gamma[q];
+                S0 += gm * st[2 * q];
+                S1 += gm * st[2 * q + 1];
             }
+            sg[2 * g] = S0;
+            sg[2 * g + 1] = S1;
+        }
+        __syncthreads();
+        for (int c = threadIdx.x; c < C; c += blockDim.x) {
+            const int g = c / cg, sgi = ns * G + g;
+            const float rs = rstd[sgi], mu = mean[sgi], S0 = sg[2 * g], S1 = sg[2 * g + 1];
+            const float ca = rs * gamma[c];
+            const float cc = -rs * rs * S1 * inv_m;
+            cof[5 * c] = ca;
+            cof[5 * c + 1] = -rs * S0 * inv_m - cc * mu;
+            cof[5 * c + 2] = cc;
+            cof[5 * c + 3] = scale[(size_t)ns * C + c];
+            cof[5 * c + 4] = shift[(size_t)ns * C + c];
+            if (blockIdx.x == 0)                                 // st[2 c ..]: this channel's {sum g, sum g * xhat}
+                publish(c, st[2 * c], st[2 * c + 1], ca, cc, rs, mu, S0, dbias ? fsums[((size_t)ns * C + c) * 2] : 0.f,
+                        dbias && fpivot ? fpivot[(size_t)ns * C + c] : 0.f);
         }
     }
     if (hf.acc != nullptr && blockIdx.x == 0 && blockIdx.y == 0) {
@@ -173,8 +245,24 @@ __global__ void k_norm_bwd_apply_fused(const TD* __restrict__ dA, const TX* __re
         const float* q = cof + 5 * (cv * V + j);
         ca[j] = q[0]; cb[j] = q[1]; cc[j] = q[2]; sc[j] = q[3]; sh[j] = q[4];
     }
-    const int p0 = blockIdx.x * chunk, p1 = min(P, p0 + chunk);
     int p = p0 + pl;
+    if constexpr (EARLY) {                       // the first four pixels: loaded ahead of the prologue
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (p + u * PL < p1) {
+                float xv[V], dv[V], o[V];
+                bf16x8_unpack(xe[u], xv);
+                bf16x8_unpack(de[u], dv);
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    const float gq = dv[j] * act_grad_pre(fmaf(xv[j], sc[j], sh[j]), act);
+                    o[j] = fmaf(ca[j], gq, fmaf(cc[j], xv[j], cb[j]));
+                }
+                VecIO<TO, V>::store(dx, ((size_t)ns * P + p + u * PL) * C + (size_t)cv * V, o);
+            }
+        }
+        p += 4 * PL;
+    }
     for (; p + 3 * PL < p1; p += 4 * PL) {       // four pixels per trip, loads first (see k_norm_stats)
         float xv[4][V], dv[4][V];
 #pragma unroll
@@ -415,37 +503,50 @@ __global__ __launch_bounds__(256, 2) void k_bn_bwd_onepass(const bf16_t* __restr
     constexpr int V = 8;
     const int CV = C / V;
     const int cv = threadIdx.x % CV, pl = threadIdx.x / CV;
-    extern __shared__ float red[];               // phase 1: 4 C constants, then PL x 2C partial sums; phase 2: 2C sums + 5C coefficients
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        red[4 * c] = scale[c];
-        red[4 * c + 1] = shift[c];
-        red[4 * c + 2] = mean[c];
-        red[4 * c + 3] = rstd[c];
+    // LDS: keep[C][3] = gamma, mean, rstd of channel c -- written once in the prologue by the thread that turns them into the channel's
+    // coefficients after the barrier (in place: no load and no exchange behind the barrier); work = phase 1: [C][2] scale, shift, then
+    // [PL][2C] partial sums
+    extern __shared__ float red[];
+    float* keep = red;
+    float* work = red + 3 * C;
+    const int p0 = blockIdx.x * chunk, p1 = min(P, p0 + chunk);
+    // Every load of the prologue is issued before the first wait -- ONE memory round trip ahead of the sums instead of two (constants,
+    // barrier, then data).  The constants go first: loads return in issue order, so the staging below waits for them alone and runs
+    // while the slot loads are still in flight.
+    const int c0 = threadIdx.x;
+    float k0[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    if (c0 < C) { k0[0] = gamma[c0]; k0[1] = mean[c0]; k0[2] = rstd[c0]; k0[3] = scale[c0]; k0[4] = shift[c0]; }
+    uint4 xq[NSLOT], dq[NSLOT];                  // (no branch around the loads: a merge would wait for them)
+#pragma unroll
+    for (int u = 0; u < NSLOT; ++u) {
+        const int p = p0 + pl + u * PL;
+        const size_t off = (size_t)(p < p1 ? p : p1 - 1) * C + (size_t)cv * V;      // (clamped: always a valid address)
+        xq[u] = *reinterpret_cast<const uint4*>(x + off);
+        dq[u] = *reinterpret_cast<const uint4*>(dA + off);
+    }
+    if (c0 < C) {
+        keep[3 * c0] = k0[0]; keep[3 * c0 + 1] = k0[1]; keep[3 * c0 + 2] = k0[2];
+        work[2 * c0] = k0[3]; work[2 * c0 + 1] = k0[4];
+    }
+    for (int c = c0 + blockDim.x; c < C; c += blockDim.x) {      // (C > 256 only)
+        keep[3 * c] = gamma[c]; keep[3 * c + 1] = mean[c]; keep[3 * c + 2] = rstd[c];
+        work[2 * c] = scale[c]; work[2 * c + 1] = shift[c];
     }
     __syncthreads();
     float sc[V], sh[V], mu[V], rs[V];
 #pragma unroll
     for (int j = 0; j < V; ++j) {
         const int c = cv * V + j;
-        sc[j] = red[4 * c]; sh[j] = red[4 * c + 1]; mu[j] = red[4 * c + 2]; rs[j] = red[4 * c + 3];
+        sc[j] = work[2 * c]; sh[j] = work[2 * c + 1]; mu[j] = keep[3 * c + 1]; rs[j] = keep[3 * c + 2];
     }
-    __syncthreads();
-    const int p0 = blockIdx.x * chunk, p1 = min(P, p0 + chunk);
-    uint4 xq[NSLOT], dq[NSLOT];
+    __syncthreads();                             // constants read: work is free for the partial sums
     if (pl < PL) {
-#pragma unroll
-        for (int u = 0; u < NSLOT; ++u) {
-            const int p = p0 + pl + u * PL;
-            const size_t off = (size_t)(p < p1 ? p : p1 - 1) * C + (size_t)cv * V;      // (clamped: always a valid address)
-            xq[u] = *reinterpret_cast<const uint4*>(x + off);
-            dq[u] = *reinterpret_cast<const uint4*>(dA + off);
-            if (p >= p1) dq[u] = make_uint4(0u, 0u, 0u, 0u);                             // dA = 0: contributes nothing
-        }
         float s1[V], s2[V];
 #pragma unroll
         for (int j = 0; j < V; ++j) s1[j] = s2[j] = 0.f;
 #pragma unroll
         for (int u = 0; u < NSLOT; ++u) {
+            if (p0 + pl + u * PL >= p1) dq[u] = make_uint4(0u, 0u, 0u, 0u);              // dA = 0: contributes nothing
             const unsigned xw[4] = {xq[u].x, xq[u].y, xq[u].z, xq[u].w}, dw[4] = {dq[u].x, dq[u].y, dq[u].z, dq[u].w};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -462,15 +563,15 @@ __global__ __launch_bounds__(256, 2) void k_bn_bwd_onepass(const bf16_t* __restr
         }
 #pragma unroll
         for (int j = 0; j < V; ++j) {
-            red[(pl * C + cv * V + j) * 2 + 0] = s1[j];
-            red[(pl * C + cv * V + j) * 2 + 1] = s2[j];
+            work[(pl * C + cv * V + j) * 2 + 0] = s1[j];
+            work[(pl * C + cv * V + j) * 2 + 1] = s2[j];
         }
     }
     __syncthreads();
     float* srep = sums2 + (size_t)(blockIdx.x % nrep) * 2 * C;
     for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {
         float a = 0.f;
-        for (int q = 0; q < PL; ++q) a += red[q * 2 * C + i];
+        for (int q = 0; q < PL; ++q) a += work[q * 2 * C + i];
         atomicAdd(&srep[i], a);
     }
     phx_grid_barrier<false>(bar, gridDim.x);      // (the only exchanged data are the atomically added sums)
@@ -479,19 +580,26 @@ __global__ __launch_bounds__(256, 2) void k_bn_bwd_onepass(const bf16_t* __restr
 #pragma unroll
     for (int u = 0; u < NSLOT; ++u)
         asm volatile("" : "+v"(xq[u].x), "+v"(xq[u].y), "+v"(xq[u].z), "+v"(xq[u].w), "+v"(dq[u].x), "+v"(dq[u].y), "+v"(dq[u].z), "+v"(dq[u].w));
-    // every block finalises for itself (k_norm_bwd_apply_fused's arithmetic, one statistic per channel: S0 = gamma t0, S1 = gamma t1)
-    float* st = red;
-    float* cof = red + 2 * C;
-    for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {
-        float a = 0.f;
-        for (int r = 0; r < nrep; ++r) a += __hip_atomic_load(sums2 + (size_t)r * 2 * C + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        st[i] = a;
-    }
-    __syncthreads();
+    // every block finalises for itself (k_norm_bwd_apply_fused's arithmetic, one statistic per channel: S0 = gamma t0, S1 = gamma t1):
+    // thread c reads the replicas of ITS channel's two sums -- four at a time in flight, added in replica order -- and turns keep[c]
+    // into the channel's coefficients in place: one round trip and one LDS stage behind the barrier
+    float* cof = keep;
     const float inv_m = 1.f / (float)P;
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        const float gm = gamma[c], r_ = rstd[c], m_ = mean[c];
-        const float t0 = st[2 * c], t1 = st[2 * c + 1];
+        float t0 = 0.f, t1 = 0.f;
+        for (int r0 = 0; r0 < nrep; r0 += 4) {
+            float v0[4], v1[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float* q = sums2 + (size_t)min(r0 + k, nrep - 1) * 2 * C + 2 * c;
+                v0[k] = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                v1[k] = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (r0 + k < nrep) { t0 += v0[k]; t1 += v1[k]; }
+        }
+        const float gm = keep[3 * c], m_ = keep[3 * c + 1], r_ = keep[3 * c + 2];
         const float S0 = gm * t0, S1 = gm * t1;
         const float ca = r_ * gm;
         const float cc = -r_ * r_ * S1 * inv_m;
@@ -646,6 +754,7 @@ static int norm_bwd_apply_launch(const void* dA, int da_dt, const void* x, int x
 #define NBA_LAUNCH(TD, TX, Vv, HNv)                                                                                               \
     do {                                                                                                                          \
         PHX_REQUIRE(too_large == 0, e_large, who_large);                                                                          \
+        PHX_REQUIRE(block_ranges_nonempty(P, chunk, nchunks), PHX_E_SHAPE, "norm_bwd_apply_fused: a block without pixels");       \
         hipLaunchKernelGGL((k_norm_bwd_apply_fused<TD, TX, TD, Vv, HNv>), dim3(nchunks, NS), dim3(threads), lds, (hipStream_t)stream, \
                            (const TD*)dA, (const TX*)x, scale, shift, mean, rstd, gamma, sums2, (TD*)dx, dgamma, dbeta, P, C, G,   \
                            PL, chunk, act, nrep, fwd_sums, fwd_pivot, dbias, hb, hf);                                             \
@@ -791,9 +900,8 @@ int phx_bn_bwd_onepass(const void* dA, const void* x, const float* scale, const 
     PHX_REQUIRE(dA && x && sums2 && barrier && dx && nrep >= 1, PHX_E_INVAL, "bn_bwd_onepass: null pointer");
     PHX_REQUIRE(bn_onepass_geometry(P, C, &PL, &threads, &chunk, &nblocks, &nslot), PHX_E_SHAPE,
                 "bn_bwd_onepass: the tensor does not fit 256 blocks x 16 pixels per thread (phx_bn_bwd_onepass_supported)");
-    size_t lds = (size_t)(PL > 2 ? PL : 2) * C * 2 * sizeof(float);
-    if (lds < (size_t)5 * C * sizeof(float)) lds = (size_t)5 * C * sizeof(float);
-    if (lds < (size_t)4 * C * sizeof(float)) lds = (size_t)4 * C * sizeof(float);
+    const size_t lds = (size_t)(3 + 2 * PL) * C * sizeof(float);       // keep[C][3] + max([C][2], [PL][2C]), PL >= 1
+    PHX_REQUIRE(lds <= 40 * 1024 && (size_t)(nblocks - 1) * chunk < (size_t)P, PHX_E_SHAPE, "bn_bwd_onepass: LDS above 40 KB or an empty block");
 #define PHX_ONEPASS(NS_, ACT_)                                                                                                      \
     hipLaunchKernelGGL((k_bn_bwd_onepass<NS_, ACT_>), dim3(nblocks), dim3(threads), lds, (hipStream_t)stream, (const bf16_t*)dA,     \
                        (const bf16_t*)x, scale, shift, mean, rstd, gamma, sums2, barrier, (bf16_t*)dx, dgamma, dbeta, P, C, PL, chunk, nrep)

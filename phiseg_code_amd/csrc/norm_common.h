@@ -25,6 +25,11 @@ static inline int block_geometry(int P, int C, int V, int NS, int ppt, int fl, i
     *nchunks = (P + *chunk - 1) / (*chunk);
     return 0;
 }
+// Every block of the launch has at least one pixel: the kernels that issue their first loads ahead of the prologue clamp them to the
+// block's last pixel, which must exist (nchunks = ceil(P / chunk) gives it; the launchers check it rather than assume it).
+static inline bool block_ranges_nonempty(int P, int chunk, int nchunks) {
+    return P >= 1 && chunk >= 1 && nchunks >= 1 && (size_t)(nchunks - 1) * (size_t)chunk < (size_t)P;
+}
 // the statistics pass (nrep == 1) and the backward reduction (nrep > 1)
 static inline int norm_geometry(int P, int C, int V, int* PL, int* threads, int* chunk, int* nchunks, int NS, int nrep = 1) {
     // Every block ends in 2C same-address fp32 atomics (~45 ns each, serialised per address): the block count is a trade between
