@@ -804,6 +804,30 @@ int phx_augment_batch_elastic(const float* images, const unsigned char* labels, 
                               float* x_out, unsigned char* s_out, void* workspace, size_t workspace_bytes, int B, int X, int Y, int A,
                               int nlabels, void* stream);
 
+/* ---- layer normalisation (tfwrapper/normalisation.py:39-68 through layers.conv2D: no gamma / beta, axes (1, 2, 3); csrc/layer_norm.hip) ----
+ * Per sample b over all N = H W C contiguous values of y [B][N]:
+ *   m = mean(y_b), r = 1 / sqrt(mean((y_b - m)^2) + eps), pre = fma(y, r, -(m r)), a = act(pre)
+ *   g = dA act'(pre), dy = r (g - mean(g) - pre mean(g pre))
+ * Every tensor is fp32 or bf16 (the dt codes), act one of PHX_ACT_*; mean / rstd [B] fp32 are written forward and read backward.
+ *   N <= phx_layer_norm_one_launch_max(): ONE launch, a block per sample; ws is not read and may be NULL.
+ *   above: TWO launches -- partial pairs ws[b][t][2] per chunk, then an apply pass that re-reduces a sample's partials in a fixed order
+ *   before it streams its chunk; ws holds phx_layer_norm_ws_floats(B, N) floats (0 for the one-launch form), need not be cleared, and
+ *   the forward and the backward call of a layer may share it.
+ *   phase 0: the whole layer (either form); 1 / 2: only the first / second launch of the split form (the engine emits them as two
+ *   entries of its launch list, each tagged with its own bytes); 1 / 2 with a one-launch N is PHX_E_INVAL.
+ * The chunk length and every summation order depend on N only and there are no float atomics: repeated calls give the same bits, with
+ * or without PHX_DETERMINISTIC, and a sample's result does not depend on B (exactly so when N % 8 == 0; otherwise for samples whose
+ * first element has the same offset from a 16-byte boundary).  Statistics are shifted sums (pivot = the sample's first value) in fp32.
+ * 16-byte accesses on the aligned body of a sample with scalar head and tail; base pointers off 16-byte alignment are read element by
+ * element.  B <= 0, N == 0, an unknown dtype or activation code, a null tensor (or ws where it is needed): PHX_E_INVAL, nothing is
+ * launched. */
+int phx_layer_norm_one_launch_max(void);
+size_t phx_layer_norm_ws_floats(int B, size_t N);
+int phx_layer_norm_fwd(const void* y, int y_dt, float eps, void* a, int a_dt, float* mean, float* rstd, float* ws, int B, size_t N, int act,
+                       int phase, void* stream);
+int phx_layer_norm_bwd(const void* dA, int dA_dt, const void* y, int y_dt, const float* mean, const float* rstd, void* dy, int dy_dt,
+                       float* ws, int B, size_t N, int act, int phase, void* stream);
+
 /* ---- data-parallel gradient exchange over RCCL / xGMI ------------------------------------------------
  * The reference is single-process, single-device (phiseg_model.py:151-157); the data-parallel design shards the batch over
  * ranks (one process per GPU) and exchanges ONE sum of the flat fp32 gradient arena per step.  RCCL is dlopen'ed on first use.

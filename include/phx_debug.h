@@ -18,6 +18,9 @@ extern "C" {
 int phx_debug_conv_policy(int large_maps, int big_tiles);
 /* persistent grid of the pair kernel (0: one work-group per CU) */
 int phx_debug_pair_kernel_grid(int blocks);
+/* layer norm (csrc/layer_norm.hip): the largest N of the one-launch forms (0: always split) and the chunk length of the split forms (a
+ * multiple of 8) -- libphx.so's constants are the measured ones; tools/bench_layer_norm.py times both forms on one shape with this */
+int phx_debug_layer_norm_policy(int one_launch_max, int chunk);
 #ifdef __cplusplus
 }
 #endif

@@ -18,11 +18,12 @@ for s in $SRCS; do
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics $EXTRA -c "$s" -o "$o" &
   fi
   OBJS="$OBJS $o"
-  # the test build libphx_dbg.so: the two translation units that hold the kernel-selection policy compiled with -DPHX_DEBUG_BUILD
-  # (phx_debug_conv_policy / phx_debug_pair_kernel_grid, include/phx_debug.h), every other object shared with libphx.so
-  if [ "$s" = "conv_mfma.hip" ] || [ "$s" = "conv_pp.hip" ]; then
+  # the test build libphx_dbg.so: the translation units that hold a kernel-selection policy compiled with -DPHX_DEBUG_BUILD
+  # (phx_debug_conv_policy / phx_debug_pair_kernel_grid / phx_debug_layer_norm_policy, include/phx_debug.h), every other object shared
+  # with libphx.so
+  if [ "$s" = "conv_mfma.hip" ] || [ "$s" = "conv_pp.hip" ] || [ "$s" = "layer_norm.hip" ]; then
     d="build_${s%.hip}_dbg.o"
-    if [ ! -f "$d" ] || [ "$s" -nt "$d" ] || [ phx_common.h -nt "$d" ] || [ conv_common.h -nt "$d" ] || [ ../../include/phx.h -nt "$d" ] || [ ../../include/phx_debug.h -nt "$d" ]; then
+    if [ ! -f "$d" ] || [ "$s" -nt "$d" ] || [ phx_common.h -nt "$d" ] || [ conv_common.h -nt "$d" ] || [ vec_io.h -nt "$d" ] || [ norm_common.h -nt "$d" ] || [ ../../include/phx.h -nt "$d" ] || [ ../../include/phx_debug.h -nt "$d" ]; then
       rm -f "$d"
       EXTRA=""
       [ "$s" = "conv_pp.hip" ] && EXTRA="-fno-slp-vectorize"

@@ -285,6 +285,8 @@ class BackwardLowering:
         permutation.  A HeadGrad dA is formed on the fly (dy_head w_head^T).  rider: the filter / bias gradient of that head
         (_head_rider_for) rides on the pair; where the pair cannot carry it, its job goes back to the heads' own launch."""
         Lb, y = self.L, sv.y
+        if sv.norm == "layer":
+            return self._layer_norm_bwd(sv, dA, dY, act)
         gamma_p, dgamma_p, dbeta_p = self._norm_grad_ptrs(sv, nv)
         if rider is not None:
             ok = (isinstance(dA, HeadGrad) and dA.dy.ptr == rider["dy"] and dA.nout == rider["nout"] and not s2d
@@ -314,6 +316,23 @@ class BackwardLowering:
                    dbeta_p, *(bias or ()), *dims,
                    tag="bytes_norm_bwd_apply" if tagged else None, flops=float(nb + y.nbytes + dY.nbytes))
 
+    def _layer_norm_bwd(self, sv, dA, dY, act):
+        """dY from dA through act and layer norm (phx_layer_norm_bwd): no variables, so no gradient but dY; a conv unit's bias gradient is
+        the per-channel sum of dY, taken by the filter stage as for a unit without normalisation."""
+        y, B = sv.y, sv.NS
+        N = y.n // B
+        ws, phases = self._layer_norm_phases(B, N)
+        for ph in phases:
+            self._emit(self.L.layer_norm_bwd, dA.ptr, dA.dt, y.ptr, y.dt, sv.mean.ptr, sv.rstd.ptr, dY.ptr, dY.dt,
+                       ws.ptr if ws is not None else None, B, N, act, ph, self.stream,
+                       tag="bytes_norm_bwd_reduce" if ph == 1 else "bytes_norm_bwd_apply",
+                       flops=float(dA.nbytes + y.nbytes + (0 if ph == 1 else dY.nbytes)))
+
+    def _bw_norm_layer(self, op, sv, dA, act):
+        dY = self._alloc(sv.y.shape, sv.y.dt)
+        self._layer_norm_bwd(sv, dA, dY, act)
+        return dY, False
+
     def _bw_norm_act(self, op):
         a, sv = op.attrs, self.saved[op]
         dA = self.grad[op.outputs[0]]
@@ -326,6 +345,9 @@ class BackwardLowering:
         if sv.route is NormRoute.INFER:
             raise NotImplementedError("backward through inference-mode batch norm is not on the hot path")
         C = sv.y.shape[3]
+        if sv.route is NormRoute.LAYER:
+            self._add_grad(op.inputs[0], write_fn=lambda g: self._layer_norm_bwd(sv, dA, g, act))
+            return
         nrep = _NREP if sv.P >= _NREP_MINP else 1
         sums2 = self._alloc_zeroed(nrep * sv.NS * C * 2)
         self._add_grad(op.inputs[0], write_fn=lambda g: self._norm_bwd(sv, a["norm_vars"], dA, g, C, act, nrep, sums2))
@@ -399,6 +421,8 @@ class BackwardLowering:
         if sv.y is None or sv.mean is None or (sv.norm == "batch" and not self.training):
             raise NotImplementedError("backward through inference-mode batch norm is not on the hot path")
         R = NormRoute
+        if sv.route is R.LAYER:
+            return self._bw_norm_layer(op, sv, dA, act)
         one_launch = {R.BN_WIDE: self._bw_norm_bn_wide, R.BN_SMALL_F32Y: self._bw_norm_bn_small, R.BN_SMALL: self._bw_norm_bn_small,
                       R.FGN: self._bw_norm_small, R.NORM_SMALL: self._bw_norm_small, R.RENORM_SMALL: self._bw_norm_bn_small}.get(sv.route) if dA.dt == BF16 else None
         if sv.route is R.RENORM_SMALL and not self.L.bn_small_supported(sv.P, sv.y.shape[3], BF16):

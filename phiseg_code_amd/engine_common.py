@@ -218,7 +218,7 @@ class RenormSaved:
 
 class NormRoute(enum.Enum):
     """How a conv unit's normalisation is lowered (engine_forward.conv_norm_route chooses; DESIGN.md section 1 has the table)."""
-    NONE, INFER_FOLDED, INFER, BN_WIDE, BN_SMALL_F32Y, BN_SMALL, FGN, NORM_SMALL, GENERIC, RENORM_SMALL = range(10)
+    NONE, INFER_FOLDED, INFER, BN_WIDE, BN_SMALL_F32Y, BN_SMALL, FGN, NORM_SMALL, GENERIC, RENORM_SMALL, LAYER = range(11)
 
 
 class StatsSource(enum.Enum):

@@ -23,6 +23,10 @@ def conv_norm_route(Lb, norm, training, bw, act_dt, x_dt, y_dt, out_dt, B, H, Wd
     fgn = _fgn_mode() if fgn is None else fgn
     if norm is None:
         return NormRoute.NONE, None
+    if norm == "layer":
+        # whole-sample statistics, no variables: always the plain materialised form on the flat kernels of csrc/layer_norm.hip (no pool /
+        # head / depth-to-space / xf / conv-epilogue form)
+        return NormRoute.LAYER, None
     per_batch = norm in ("batch", "renorm")        # statistics over the whole batch (NS = 1)
     NS, P = (1, B * H * Wd) if per_batch else (B, H * Wd)
     if norm == "batch" and not training:
@@ -176,7 +180,11 @@ class ForwardLowering:
     # ---- the generic normalisation lowering, shared by the conv units, the transposed / general units and norm_act --------------
     def _norm_vectors(self, sv, B, HW, C, num_groups):
         """Statistics geometry of sv.norm on a [B, HW, C] tensor -- NS statistics sets of P values per channel, G groups -- and the
-        four per-layer vectors, all recorded on `sv`."""
+        four per-layer vectors, all recorded on `sv`.  Layer norm: one statistics set per sample over all HW * C values, no scale / shift."""
+        if sv.norm == "layer":
+            sv.NS, sv.P, sv.G = B, HW, 1
+            sv.mean, sv.rstd = self._alloc((B,), F32), self._alloc((B,), F32)
+            return
         if sv.norm in ("batch", "renorm"):
             sv.NS, sv.P, sv.G = 1, B * HW, C
         else:
@@ -237,6 +245,9 @@ class ForwardLowering:
         """out = act(norm(y)) the generic way: inference-mode batch norm as scale / shift + phx_affine_act, anything else as a
         statistics pass + the fused apply.  `conv`: the launch that writes y, where the caller has not emitted it yet."""
         S, Lb, nv = self.stream, self.L, a["norm_vars"]
+        if sv.norm == "layer":
+            conv()
+            return self._layer_norm_fwd(sv, y, out, act)
         if sv.norm == "batch" and not training:
             self._emit(Lb.bn_infer_scale_shift, self.store.ptr(nv["gamma"]), self.store.ptr(nv["beta"]), self.store.ptr(nv["moving_mean"]),
                        self.store.ptr(nv["moving_variance"]), tfnorm.EPS[sv.norm], C, sv.scale.ptr, sv.shift.ptr, S)
@@ -249,6 +260,21 @@ class ForwardLowering:
             self._renorm_setup(sv, nv, C)
             return self._renorm_apply(sv, nv, y, sums, pivot, out, C, act)
         self._emit(Lb.norm_apply_fused, *self._norm_apply_args(sv, a, y, sums, pivot, out, C, act, training), S)
+
+    def _layer_norm_phases(self, B, N):
+        """-> (workspace or None, phases): a one-launch layer is ONE entry of the launch list (phase 0), a split one two (phases 1, 2),
+        so that an entry is a kernel launch and carries its own bytes."""
+        n = int(self.L.layer_norm_ws_floats(B, N))
+        return (self._alloc((n,), F32), (1, 2)) if n else (None, (0,))
+
+    def _layer_norm_fwd(self, sv, y, out, act):
+        """out = act(layer_norm(y)) on the flat per-sample kernels (phx_layer_norm_fwd); mean / rstd [B] stay on sv for the backward pass."""
+        B, N = sv.NS, y.n // sv.NS
+        ws, phases = self._layer_norm_phases(B, N)
+        for ph in phases:
+            self._emit(self.L.layer_norm_fwd, y.ptr, y.dt, tfnorm.EPS["layer"], out.ptr, out.dt, sv.mean.ptr, sv.rstd.ptr,
+                       ws.ptr if ws is not None else None, B, N, act, ph, self.stream, tag="bytes_norm_apply",
+                       flops=float(y.nbytes + (0 if ph == 1 else out.nbytes)))
 
     def _fw_tconv_unit(self, op, bw):
         """tf.nn.conv2d_transpose -> [bias] -> [norm] -> act (tfwrapper/layers.py:197-258) on the direct kernels of tconv.hip;
@@ -282,7 +308,7 @@ class ForwardLowering:
         y = sv.y = self._alloc(out.shape, out.dt)
         self._emit(conv_fwd, x.ptr, x.dt, wptr, bptr, y.ptr, y.dt, *geo, 0, S)
         self._norm_vectors(sv, B, out.shape[1] * out.shape[2], cout, a["num_groups"])
-        sv.route = NormRoute.INFER if (norm == "batch" and not training) else NormRoute.GENERIC
+        sv.route = NormRoute.INFER if (norm == "batch" and not training) else (NormRoute.LAYER if norm == "layer" else NormRoute.GENERIC)
         self._norm_fwd(sv, a, y, out, cout, act, training)
 
     # ---- fused latent heads: mu = conv1x1(x), sigma = softplus(conv1x1(x)), z = mu + sigma * eps (posteriors.py:125-128,
@@ -512,8 +538,9 @@ class ForwardLowering:
         o.y = self._alloc(o.out.shape, o.out.dt)
         self._norm_vectors(sv, o.B, o.H * o.Wd, o.cout, a["num_groups"])
         nv = a["norm_vars"]
-        o.params = (self.store.ptr(nv["gamma"]), self.store.ptr(nv["beta"]), tfnorm.EPS[sv.norm])
-        o.moving = self._moving_args(nv, sv.norm == "batch" and o.training and self.loss is not None)
+        if sv.norm != "layer":                   # (layer norm has no variables)
+            o.params = (self.store.ptr(nv["gamma"]), self.store.ptr(nv["beta"]), tfnorm.EPS[sv.norm])
+            o.moving = self._moving_args(nv, sv.norm == "batch" and o.training and self.loss is not None)
         if sv.norm == "renorm":
             self._renorm_setup(sv, nv, o.cout)
         sv.route, o.stats = conv_norm_route(self.L, sv.norm, o.training, bw, self.act_dt, o.x.dt, o.y.dt, o.out.dt, o.B, o.H, o.Wd, sv.cin_eff,
@@ -685,6 +712,11 @@ class ForwardLowering:
         y, out, nv = o.y, o.out, o.a["norm_vars"]
         self._emit(self.L.renorm_small_fwd, y.ptr, y.dt, *o.params, out.ptr, out.dt, sv.mean.ptr, sv.rstd.ptr, sv.scale.ptr, sv.shift.ptr,
                    *self._renorm_args(sv, nv), sv.P, o.cout, o.act, self.stream, tag="bytes_norm_apply", flops=float(y.nbytes + out.nbytes))
+
+    def _fw_unit_layer(self, o, sv):
+        # layer norm: the convolution writes y (bias in, activation off, no statistics epilogue), then the flat per-sample kernels
+        self._conv_into(o, o.y, 0)
+        self._layer_norm_fwd(sv, o.y, o.out, o.act)
 
     def _fw_unit_fgn(self, o, sv):
         # maps of at most 16 x 16: convolution, bias, group / instance norm and activation in ONE launch (a block holds whole
@@ -863,7 +895,7 @@ class ForwardLowering:
             return
         sv.y = x
         self._norm_vectors(sv, B, HW, C, a["num_groups"])
-        sv.route = NormRoute.INFER if (norm == "batch" and not training) else NormRoute.GENERIC
+        sv.route = NormRoute.INFER if (norm == "batch" and not training) else (NormRoute.LAYER if norm == "layer" else NormRoute.GENERIC)
         self._norm_fwd(sv, a, x, out, C, act, training)
 
     def _fw_flatten(self, op, bw):

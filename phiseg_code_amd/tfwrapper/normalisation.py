@@ -38,8 +38,10 @@ def identity(x, **kwargs):
     return x
 
 
-def layer_norm(x, **kwargs):
-    raise NotImplementedError("layer_norm has no call site in phiseg/ (out of scope, SURVEY.md section 2)")
+def layer_norm(x, gamma=None, beta=None, axes=(1, 2, 3), eps=1e-3, scope='layer_norm', **kwargs):
+    """normalisation.py:39-68 as conv2D calls it (gamma = beta = None, axes (1, 2, 3), eps 1e-3): per sample over all H W C values, no
+    variables, no train / inference switch (`training` in kwargs is accepted and ignored)."""
+    return _standalone("layer_norm")(x)
 
 
 def batch_renorm(x, training=None, moving_average_decay=0.99, scope="batch_renorm", **kwargs):
@@ -48,8 +50,8 @@ def batch_renorm(x, training=None, moving_average_decay=0.99, scope="batch_renor
     return _standalone("batch_renorm")(x)
 
 
-KIND = {batch_norm: "batch", group_norm2D: "group", instance_norm2D: "instance", identity: None, batch_renorm: "renorm"}
-EPS = {"batch": 1e-3, "group": 1e-5, "instance": 1e-5, "renorm": 1e-3}
+KIND = {batch_norm: "batch", group_norm2D: "group", instance_norm2D: "instance", identity: None, batch_renorm: "renorm", layer_norm: "layer"}
+EPS = {"batch": 1e-3, "group": 1e-5, "instance": 1e-5, "renorm": 1e-3, "layer": 1e-3}
 BN_DECAY = 0.99
 RENORM_DECAY = 0.99                 # renorm_decay (the reference's moving_average_decay goes here)
 RENORM_MOVING_DECAY = 0.999         # contrib's default `decay`, which the reference leaves alone: the moving statistics' decay
@@ -74,7 +76,8 @@ def renorm_clip(step):
 
 def make_variables(kind, channels, scope=None):
     """Create the norm's variables inside the CURRENT scope (the conv's name scope); `scope` replaces the callable's default
-    scope name (batch_norm / batch_renorm / group_norm / instance_norm), as the residual units pass scope='bn1' (layers.py:452-456)."""
+    scope name (batch_norm / batch_renorm / group_norm / instance_norm), as the residual units pass scope='bn1' (layers.py:452-456).
+    "layer" (and None) has no variables: nothing is created."""
     g = G.get_default_graph()
     if kind == "batch":
         with g.variable_scope(scope or "batch_norm"):

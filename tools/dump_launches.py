@@ -17,10 +17,12 @@ from tests.helpers import load_golden  # noqa: E402
 from tests.test_graph_cpu import make_config  # noqa: E402
 
 
-def model_plan(golden, dt, B=None, norm=None, what="train", momentum=False):
+def model_plan(golden, dt, B=None, norm=None, what="train", momentum=False, norm_fn=None):
     _, cfg, _ = load_golden(golden)
     cfg = dict(cfg, B=B or cfg["B"], **({"norm": norm} if norm else {}))
     c = make_config(cfg, dt)
+    if norm_fn is not None:             # a normaliser the fixtures' config table does not name
+        c.layer_norm = norm_fn
     if momentum:
         c.optimizer = optimizers.MomentumOptimizer
     m = phiseg_model.phiseg(c, rng_seed=cfg["eps_seed"])
@@ -69,8 +71,10 @@ CASES = {"lidc_bf16_b2": lambda: model_plan("lidc_phiseg_bn", "bf16", 2), "lidc_
          "tiny_f32": lambda: model_plan("tiny_phiseg_bn", "f32"), "lidc_f32_infer": lambda: model_plan("lidc_phiseg_bn", "f32", what="infer"), "lidc_bf16_infer": lambda: model_plan("lidc_phiseg_bn", "bf16", 2, what="infer"),
          "lidc_bf16_sample": lambda: model_plan("lidc_phiseg_bn", "bf16", 2, what="sample"), "probunet_bf16": lambda: model_plan("tiny_probunet_bn", "bf16"),
          "detunet_bf16": lambda: model_plan("tiny_detunet_bn", "bf16"), "lidc_bf16_momentum": lambda: model_plan("lidc_phiseg_bn", "bf16", 2, momentum=True),
-         "tiny_f32_momentum": lambda: model_plan("tiny_phiseg_bn", "f32", momentum=True)}
-for _n in ("identity", "batch_norm", "group_norm2D"):
+         "tiny_f32_momentum": lambda: model_plan("tiny_phiseg_bn", "f32", momentum=True),
+         "lidc_bf16_ln": lambda: model_plan("lidc_phiseg_bn", "bf16", 2, norm_fn=tfnorm.layer_norm),
+         "lidc_f32_ln": lambda: model_plan("lidc_phiseg_bn", "f32", norm_fn=tfnorm.layer_norm)}
+for _n in ("identity", "batch_norm", "group_norm2D", "layer_norm"):
     CASES["extra_" + _n] = lambda n=_n: layer_plan("extra", n)
     CASES["residual_" + _n] = lambda n=_n: layer_plan("residual", n)
 
