@@ -828,6 +828,58 @@ int phx_layer_norm_fwd(const void* y, int y_dt, float eps, void* a, int a_dt, fl
 int phx_layer_norm_bwd(const void* dA, int dA_dt, const void* y, int y_dt, const float* mean, const float* rstd, void* dy, int dy_dt,
                        float* ws, int B, size_t N, int act, int phase, void* stream);
 
+/* ---- the 3-D layer family (tfwrapper/layers.py:31-41, 148-194, 261-323, 348-376, 609-612; csrc/conv3d.hip) --------------------
+ * NDHWC activations [B, D, H, W, C], fp32 or bf16 (the dt codes); fp32 filters, fp32 accumulation; no floating-point atomics, every
+ * reduction in a fixed order: repeated calls give the same bits with or without PHX_DETERMINISTIC.  SAME padding with TF's rule
+ * per axis: out = ceil(in / s), total = max((out - 1) s + k - in, 0), before = total / 2.  A non-positive size or an unsupported
+ * window returns PHX_E_SHAPE and launches nothing.
+ *
+ * conv3D: x [B,D,H,W,Cin] -> y [B, ceil(D/sd), ceil(H/sh), ceil(W/sw), Cout] (phx_gconv3d_out_size), filter w_dhwio
+ * [kd][kh][kw][Cin][Cout], any kernel extent and stride, no dilation; optional bias and activation in the forward epilogue.  dgrad
+ * writes dx [B,D,H,W,Cin]; wgrad ACCUMULATES into dw_dhwio (the bias gradient is phx_channel_sum_accumulate of dy).  Forward and
+ * dgrad take a vector path when the channel count they reduce over (Cin forward, Cout in dgrad) is a multiple of 4 (fp32 input)
+ * or 8 (bf16 input): 16-byte channel reads, 8 output channels of 4 voxels per thread, the filter staged in LDS; any other count
+ * runs one thread per output element. */
+int phx_gconv3d_out_size(int D, int H, int W, int sd, int sh, int sw, int* Do, int* Ho, int* Wo);
+int phx_gconv3d_fwd(const void* x, int x_dt, const float* w_dhwio, const float* bias, void* y, int y_dt, int B, int D, int H, int W,
+                    int Cin, int Cout, int kd, int kh, int kw, int sd, int sh, int sw, int act, void* stream);
+int phx_gconv3d_dgrad(const void* dy, int dy_dt, const float* w_dhwio, void* dx, int dx_dt, int B, int D, int H, int W, int Cin,
+                      int Cout, int kd, int kh, int kw, int sd, int sh, int sw, void* stream);
+int phx_gconv3d_wgrad(const void* x, int x_dt, const void* dy, int dy_dt, float* dw_dhwio, int B, int D, int H, int W, int Cin,
+                      int Cout, int kd, int kh, int kw, int sd, int sh, int sw, void* stream);
+/* transposed_conv3D = tf.nn.conv3d_transpose, SAME: x [B,D,H,W,Cin] -> y [B, D sd, H sh, W sw, Cout], filter w_dhwoi
+ * [kd][kh][kw][Cout][Cin] (TF's layout); the padding is that of the convolution this is the input gradient of, per axis
+ * total = max(k - s, 0), before = total / 2.  dgrad: dy [B, D sd, H sh, W sw, Cout] -> dx [B,D,H,W,Cin]; wgrad ACCUMULATES. */
+int phx_tconv3d_fwd(const void* x, int x_dt, const float* w_dhwoi, const float* bias, void* y, int y_dt, int B, int D, int H, int W,
+                    int Cin, int Cout, int kd, int kh, int kw, int sd, int sh, int sw, int act, void* stream);
+int phx_tconv3d_dgrad(const void* dy, int dy_dt, const float* w_dhwoi, void* dx, int dx_dt, int B, int D, int H, int W, int Cin,
+                      int Cout, int kd, int kh, int kw, int sd, int sh, int sw, void* stream);
+int phx_tconv3d_wgrad(const void* x, int x_dt, const void* dy, int dy_dt, float* dw_dhwoi, int B, int D, int H, int W, int Cin,
+                      int Cout, int kd, int kh, int kw, int sd, int sh, int sw, void* stream);
+/* maxpool3D = tf.nn.max_pool3d, window = stride = (pd, ph, pw), each entry 1 or 2, SAME (padding on the far side only):
+ * y [B, ceil(D/pd), ceil(H/ph), ceil(W/pw), C]; the gradient goes to the first maximum of each window in row-major (d, h, w)
+ * order and every element of dx is written */
+int phx_maxpool3d_fwd(const void* x, int dt, void* y, int B, int D, int H, int W, int C, int pd, int ph, int pw, void* stream);
+int phx_maxpool3d_bwd(const void* x, const void* dy, int dt, void* dx, int B, int D, int H, int W, int C, int pd, int ph, int pw,
+                      void* stream);
+/* bilinear_upsample3D, factor 2 on three axes: tf.image.resize_bilinear (legacy coordinates, align_corners = False) on the (H, W)
+ * planes and then along D, i.e. per axis up[2k] = x[k], up[2k + 1] = (x[k] + x[min(k + 1, n - 1)]) / 2.  x [B,D,H,W,C] ->
+ * y [B,2D,2H,2W,C] in one launch; _bwd is the adjoint (dy [B,2D,2H,2W,C] -> dx [B,D,H,W,C], a gather: no atomics), _bwd_acc ADDS
+ * it to dx (a tensor with several readers) */
+int phx_bilinear_up2x_3d_fwd(const void* x, int dt, void* y, int B, int D, int H, int W, int C, void* stream);
+int phx_bilinear_up2x_3d_bwd(const void* dy, int dt, void* dx, int B, int D, int H, int W, int C, void* stream);
+int phx_bilinear_up2x_3d_bwd_acc(const void* dy, int dt, void* dx, int B, int D, int H, int W, int C, void* stream);
+/* dst[b, z, y, x, :] = src[b, z + off_z, y + off_y, x + off_x, :] inside the source, 0 outside (the 5-D centre crop of
+ * crop_and_concat); the gradient is the same call with the sizes swapped and the offsets negated */
+int phx_spatial_window3d(const void* src, void* dst, int dt, int B, int Ds, int Hs, int Ws, int Dd, int Hd, int Wd, int C, int off_z,
+                         int off_y, int off_x, void* stream);
+/* Moving statistics of a batch norm on a rank-5 tensor.  [TF 1.12 semantics, believed] tf.contrib.layers.batch_norm fuses only
+ * rank 2 and 4; on rank 5 its non-fused path updates the moving variance with the BIASED batch variance (the fused path applies
+ * Bessel's correction).  mean / rstd [C] are the vectors the layer's apply launch published (var = 1 / rstd^2 - eps):
+ * moving -= (moving - batch) * momentum. */
+int phx_bn_moving_update_biased(const float* mean, const float* rstd, float eps, float* moving_mean, float* moving_var, float momentum,
+                                int C, void* stream);
+
 /* ---- data-parallel gradient exchange over RCCL / xGMI ------------------------------------------------
  * The reference is single-process, single-device (phiseg_model.py:151-157); the data-parallel design shards the batch over
  * ranks (one process per GPU) and exchanges ONE sum of the flat fp32 gradient arena per step.  RCCL is dlopen'ed on first use.

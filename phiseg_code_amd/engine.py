@@ -674,7 +674,7 @@ class Plan(ForwardLowering, BackwardLowering):
             self._cur = self.launches
 
 
-    _VIRTUAL = ("one_hot", "sub_const", "random_normal", "mul", "nn_resize")
+    _VIRTUAL = ("one_hot", "sub_const", "random_normal", "mul", "nn_resize", "fold_depth")
 
 
 

@@ -236,6 +236,27 @@ class BackwardLowering:
         self._add_grad(op.inputs[0], write_fn=lambda g: self._emit(
             self.L.maxpool2x2_bwd, x.ptr, d.ptr, d.dt, g.ptr, x.shape[0], x.shape[1], x.shape[2], x.shape[3], self.stream))
 
+    def _bw_max_pool3d(self, op):
+        x, d = self.val[op.inputs[0]], self.grad[op.outputs[0]]
+        self._add_grad(op.inputs[0], write_fn=lambda g: self._emit(
+            self.L.maxpool3d_bwd, x.ptr, d.ptr, d.dt, g.ptr, *x.shape, *op.attrs["window"], self.stream))
+
+    def _bw_bilinear_up3d(self, op):
+        x, d = self.val[op.inputs[0]], self.grad[op.outputs[0]]
+        self._add_grad(op.inputs[0], write_fn=lambda g: self._emit(self.L.bilinear_up2x_3d_bwd, d.ptr, d.dt, g.ptr, *x.shape, self.stream),
+                       accum_fn=(lambda g: self._emit(self.L.bilinear_up2x_3d_bwd_acc, d.ptr, d.dt, g.ptr, *x.shape, self.stream))
+                       if d.dt == x.dt else None)
+
+    def _bw_spatial_window3d(self, op):
+        x, d = self.val[op.inputs[0]], self.grad[op.outputs[0]]
+        oz, oy, ox = op.attrs["off"]
+        self._add_grad(op.inputs[0], write_fn=lambda g: self._emit(
+            self.L.spatial_window3d, d.ptr, g.ptr, d.dt, x.shape[0], *d.shape[1:4], *x.shape[1:4], x.shape[4], -oz, -oy, -ox, self.stream))
+
+    def _bw_fold_depth(self, op):
+        x, d = self.val[op.inputs[0]], self.grad[op.outputs[0]]
+        self._add_grad(op.inputs[0], buf=Buf(x.shape, d.dt, like=d.t))
+
     def _bw_spatial_window(self, op):
         x, d = self.val[op.inputs[0]], self.grad[op.outputs[0]]
         oy, ox = op.attrs["off"]
@@ -391,6 +412,8 @@ class BackwardLowering:
         db = self.store.grad_ptr(b) if (b is not None and not db_done) else None
         if sv.upconv is not None:
             return self._bw_unit_upconv(op, sv, dY, db)
+        if sv.volume is not None:
+            return self._bw_unit_volume(op, sv, dY, db)
         if sv.general is not None:
             return self._bw_unit_general(op, sv, dY, db)
         if sv.transposed is not None:
@@ -499,9 +522,11 @@ class BackwardLowering:
             _, wd_w = self._packed(W)
             self._add_grad(xin, write_fn=lambda g: upconv.backward_data(self._emit, self._alloc, Lb, S, upc, dY, wd_w, g, B, h, w, cin, cout))
 
-    def _bw_unit_direct(self, op, sv, dY, db, wgrad, dgrad):
-        """Filter, bias and data gradient of a unit on the direct kernels (gconv.hip / tconv.hip) with the geometry saved forward."""
-        S, x, W, cout = self.stream, sv.x, op.attrs["W"], self._unit_dims(op, sv)[4]
+    def _bw_unit_direct(self, op, sv, dY, db, wgrad, dgrad, cout=None):
+        """Filter, bias and data gradient of a unit on the direct kernels (gconv.hip / tconv.hip / conv3d.hip) with the geometry saved
+        forward."""
+        S, x, W = self.stream, sv.x, op.attrs["W"]
+        cout = cout or self._unit_dims(op, sv)[4]
         self._emit(wgrad, x.ptr, x.dt, dY.ptr, dY.dt, self.store.grad_ptr(W), *sv.geo, S)
         if db is not None:
             self._emit(self.L.channel_sum_accumulate, dY.ptr, dY.dt, db, dY.n // cout, cout, S)
@@ -510,6 +535,11 @@ class BackwardLowering:
 
     def _bw_unit_general(self, op, sv, dY, db):
         self._bw_unit_direct(op, sv, dY, db, self.L.gconv2d_wgrad, self.L.gconv2d_dgrad)
+
+    def _bw_unit_volume(self, op, sv, dY, db):
+        Lb = self.L
+        wgrad, dgrad = (Lb.gconv3d_wgrad, Lb.gconv3d_dgrad) if sv.volume[0] == "conv" else (Lb.tconv3d_wgrad, Lb.tconv3d_dgrad)
+        self._bw_unit_direct(op, sv, dY, db, wgrad, dgrad, cout=sv.geo[5])
 
     def _bw_unit_transposed(self, op, sv, dY, db):
         self._bw_unit_direct(op, sv, dY, db, self.L.tconv2d_wgrad, self.L.tconv2d_dgrad)

@@ -129,7 +129,7 @@ class ForwardLowering:
                 and len(va.shape) == 4 and va.shape[-1] % 32 == 0 and vb.shape[-1] % 32 == 0 and len(cons) == 1 and ot not in self.fetches):
             c = cons[0]
             ca = c.attrs if c.type == "conv_unit" else None
-            if (ca is not None and ca["ksize"] == 3 and ca.get("transposed") is None and ca.get("general") is None
+            if (ca is not None and ca["ksize"] == 3 and ca.get("transposed") is None and ca.get("general") is None and ca.get("volume") is None
                     and ca["W"].shape[-1] % 32 == 0 and self.op_lane.get(c) == self.op_lane.get(op) and c not in self._lat):
                 # concat-free: the one reader, a 3x3 convolution on the MFMA path, takes the two tensors as they are (no launch here)
                 self.val[ot] = DualBuf(va, vb)
@@ -232,7 +232,7 @@ class ForwardLowering:
         nv = a["norm_vars"]
         return (y.ptr, y.dt, sums.ptr, pivot.ptr if pivot is not None else None, self.store.ptr(nv["gamma"]), self.store.ptr(nv["beta"]),
                 tfnorm.EPS[sv.norm], out.ptr, out.dt, sv.mean.ptr, sv.rstd.ptr, sv.scale.ptr, sv.shift.ptr,
-                *self._moving_args(nv, sv.norm == "batch" and training and self.loss is not None), sv.NS, sv.P, C, sv.G, act)
+                *self._moving_args(nv, sv.norm == "batch" and training and self.loss is not None and sv.volume is None), sv.NS, sv.P, C, sv.G, act)
 
     def _norm_stats_pass(self, sv, y, sums, C, conv=_noop):
         """Shifted (pivot) sums of y in a stand-alone pass, behind the launch `conv` that writes y (if any); -> the pivot vector."""
@@ -278,13 +278,21 @@ class ForwardLowering:
 
     def _fw_tconv_unit(self, op, bw):
         """tf.nn.conv2d_transpose -> [bias] -> [norm] -> act (tfwrapper/layers.py:197-258) on the direct kernels of tconv.hip;
-        the normalisation runs as statistics pass + fused apply on the up-sampled tensor."""
+        the normalisation runs as statistics pass + fused apply on the up-sampled tensor.  The general 2-D units (gconv.hip) and the 3-D
+        units (conv3d.hip) take the same form."""
         a = op.attrs
         x = self.val[op.inputs[0]]
         W, b = a["W"], a["b"]
         B, H, Wd = x.shape[0], x.shape[1], x.shape[2]
         S, Lb = self.stream, self.L
-        if a.get("general") is not None:
+        vol = a.get("volume")
+        if vol is not None:
+            # conv3D / transposed_conv3D on the kernels of csrc/conv3d.hip: x is [B, D, H, W, C], filter DHWIO / DHWOI
+            form = vol[0]
+            cin, cout = (W.shape[3], W.shape[4]) if form == "conv" else (W.shape[4], W.shape[3])
+            geo = tuple(x.shape[:4]) + (cin, cout) + tuple(vol[1:])
+            conv_fwd = Lb.gconv3d_fwd if form == "conv" else Lb.tconv3d_fwd
+        elif a.get("general") is not None:
             # strided / dilated SAME convolution on the direct kernels of gconv.hip (conv2D with strides, dilated_conv2D,
             # dense_layer as a 1x1 convolution of the flattened input); filter HWIO (a dense layer's [F, U] is [1][1][F][U])
             geo = (B, H, Wd, W.shape[-2], W.shape[-1]) + tuple(a["general"])
@@ -301,15 +309,31 @@ class ForwardLowering:
         training = a["training"] if isinstance(a["training"], bool) else self.training
         norm = self._lowered_norm(a, training)
         wptr, bptr = self.store.ptr(W), (self.store.ptr(b) if b is not None else None)
-        sv = self.saved[op] = ConvSaved.plain(x, out, norm, cin, transposed=a.get("transposed"), general=a.get("general"), geo=geo)
+        sv = self.saved[op] = ConvSaved.plain(x, out, norm, cin, transposed=a.get("transposed"), general=a.get("general"), volume=vol, geo=geo)
         if norm is None:
             self._emit(conv_fwd, x.ptr, x.dt, wptr, bptr, out.ptr, out.dt, *geo, act, S)
             return
-        y = sv.y = self._alloc(out.shape, out.dt)
+        # (a volume's pre-normalisation tensor is kept in the folded shape [B, D H, W, C]: the normalisation passes see [B, pixels, C])
+        y = sv.y = self._alloc(self._folded(out.shape), out.dt)
         self._emit(conv_fwd, x.ptr, x.dt, wptr, bptr, y.ptr, y.dt, *geo, 0, S)
-        self._norm_vectors(sv, B, out.shape[1] * out.shape[2], cout, a["num_groups"])
+        self._norm_vectors(sv, B, int(np.prod(out.shape[1:-1])), cout, a["num_groups"])
         sv.route = NormRoute.INFER if (norm == "batch" and not training) else (NormRoute.LAYER if norm == "layer" else NormRoute.GENERIC)
         self._norm_fwd(sv, a, y, out, cout, act, training)
+        self._moving_biased(sv, a, cout, training)
+
+    @staticmethod
+    def _folded(shape):
+        """[B, D, H, W, C] -> [B, D H, W, C] (the same memory); a 4-D shape as it is."""
+        return tuple(shape) if len(shape) != 5 else (shape[0], shape[1] * shape[2], shape[3], shape[4])
+
+    def _moving_biased(self, sv, a, C, training):
+        """Batch norm on a rank-5 tensor moves its moving pair with the BIASED batch variance (tf.contrib.layers.batch_norm's non-fused
+        path): the apply launch got no moving pointers (_norm_apply_args), this launch updates the pair from the
+        statistics it published."""
+        if sv.volume is not None and sv.norm == "batch" and training and self.loss is not None:
+            nv = a["norm_vars"]
+            self._emit(self.L.bn_moving_update_biased, sv.mean.ptr, sv.rstd.ptr, tfnorm.EPS["batch"], self.store.ptr(nv["moving_mean"]),
+                       self.store.ptr(nv["moving_variance"]), 1.0 - tfnorm.BN_DECAY, C, self.stream)
 
     # ---- fused latent heads: mu = conv1x1(x), sigma = softplus(conv1x1(x)), z = mu + sigma * eps (posteriors.py:125-128,
     # priors.py:117-120) as one launch forward (phx_latent_heads_fwd) and one backward (phx_latent_heads_bwd) ----------------------
@@ -320,7 +344,7 @@ class ForwardLowering:
 
         def is_head(op, act):
             a = op.attrs
-            if op.type != "conv_unit" or a.get("transposed") is not None or a.get("general") is not None:
+            if op.type != "conv_unit" or a.get("transposed") is not None or a.get("general") is not None or a.get("volume") is not None:
                 return False
             W = a["W"]
             return (a["ksize"] == 1 and a["norm"] is None and a["b"] is not None and a["act"] == act and W.shape[-1] in (2, 4, 6)
@@ -387,7 +411,7 @@ class ForwardLowering:
 
         def plain_1x1(op):
             a = op.attrs
-            return (op.type == "conv_unit" and a.get("transposed") is None and a.get("general") is None and a["ksize"] == 1
+            return (op.type == "conv_unit" and a.get("transposed") is None and a.get("general") is None and a.get("volume") is None and a["ksize"] == 1
                     and op not in self._lat)
         for tb in ops:
             if tb.type != "tile_batch" or len(tb.inputs[0].shape) != 4:
@@ -485,7 +509,7 @@ class ForwardLowering:
         if len(cons) != 1 or cons[0].type != "conv_unit" or cons[0] in self._lat:
             return None
         c, ca = cons[0], cons[0].attrs
-        if (ca.get("transposed") is not None or ca.get("general") is not None or ca["ksize"] != 1 or ca["norm"] is not None
+        if (ca.get("transposed") is not None or ca.get("general") is not None or ca.get("volume") is not None or ca["ksize"] != 1 or ca["norm"] is not None
                 or ca["b"] is None or ca["act"] != "identity" or c.inputs[0] is not out or c.outputs[0].kind != G.KIND_F32
                 or c.outputs[0] in self.fetches or self.op_lane.get(c) != self.op_lane.get(op)):
             return None
@@ -505,7 +529,7 @@ class ForwardLowering:
             return False
         for c in cons:
             ca = c.attrs
-            if (c.type != "conv_unit" or c in self._lat or ca.get("transposed") is not None or ca.get("general") is not None
+            if (c.type != "conv_unit" or c in self._lat or ca.get("transposed") is not None or ca.get("general") is not None or ca.get("volume") is not None
                     or ca["ksize"] != 3 or ca["norm"] != "batch" or ca["b"] is not None or c.inputs[0] is not out):
                 return False
             tr = ca["training"] if isinstance(ca["training"], bool) else self.training
@@ -518,7 +542,7 @@ class ForwardLowering:
     def _fw_conv_unit(self, op, bw):
         """conv -> [bias] -> [norm] -> act: prepare the operands, choose the normalisation route (conv_norm_route), emit that route."""
         a = op.attrs
-        if a.get("transposed") is not None or a.get("general") is not None:
+        if a.get("transposed") is not None or a.get("general") is not None or a.get("volume") is not None:
             return self._fw_tconv_unit(op, bw)
         if op in self._norm_head:                # its forward ran inside the producer's apply pass
             self.saved[op] = ConvSaved.plain(self.val[op.inputs[0]], self.val[op.outputs[0]], None, a["W"].shape[-2], head1x1=True, norm_head=True)
@@ -838,6 +862,28 @@ class ForwardLowering:
         self.val[op.outputs[0]] = out
         self._emit(self.L.maxpool2x2_fwd, x.ptr, x.dt, out.ptr, x.shape[0], x.shape[1], x.shape[2], x.shape[3], self.stream)
 
+    def _fw_max_pool3d(self, op, bw):
+        x = self.val[op.inputs[0]]
+        out = self._alloc(self._cshape(op.outputs[0]), x.dt)
+        self.val[op.outputs[0]] = out
+        self._emit(self.L.maxpool3d_fwd, x.ptr, x.dt, out.ptr, *x.shape, *op.attrs["window"], self.stream)
+
+    def _fw_bilinear_up3d(self, op, bw):
+        x = self.val[op.inputs[0]]
+        out = self._alloc(self._cshape(op.outputs[0]), x.dt)
+        self.val[op.outputs[0]] = out
+        self._emit(self.L.bilinear_up2x_3d_fwd, x.ptr, x.dt, out.ptr, *x.shape, self.stream)
+
+    def _fw_spatial_window3d(self, op, bw):
+        x = self.val[op.inputs[0]]
+        out = self._alloc(self._cshape(op.outputs[0]), x.dt)
+        self.val[op.outputs[0]] = out
+        self._emit(self.L.spatial_window3d, x.ptr, out.ptr, x.dt, *x.shape[:4], *out.shape[1:4], x.shape[4], *op.attrs["off"], self.stream)
+
+    def _fw_fold_depth(self, op, bw):
+        x = self.val[op.inputs[0]]
+        self.val[op.outputs[0]] = Buf(self._cshape(op.outputs[0]), x.dt, like=x.t)      # same memory, new shape
+
     def _fw_spatial_window(self, op, bw):
         x = self.val[op.inputs[0]]
         out = self._alloc(self._cshape(op.outputs[0]), x.dt)
@@ -881,12 +927,15 @@ class ForwardLowering:
         x = self.val[op.inputs[0]]
         out = self._alloc(x.shape, x.dt)
         self.val[op.outputs[0]] = out
+        vol = ("norm",) if len(x.shape) == 5 else None
+        if vol is not None:                      # a volume: the same memory as [B, D H, W, C]
+            x = Buf(self._folded(x.shape), x.dt, like=x.t)
         B, C = x.shape[0], x.shape[3]
         HW = x.shape[1] * x.shape[2]
         act = rt.ACT_CODES[a["act"]]
         training = a["training"] if isinstance(a["training"], bool) else self.training
         norm = self._lowered_norm(a, training)
-        sv = self.saved[op] = ConvSaved.plain(x, out, norm, C)
+        sv = self.saved[op] = ConvSaved.plain(x, out, norm, C, volume=vol)
         if norm is None:
             ones = Buf((C,), F32, like=torch.ones(C, dtype=torch.float32, device=_device()))
             zeros = Buf((C,), F32, like=torch.zeros(C, dtype=torch.float32, device=_device()))
@@ -897,6 +946,7 @@ class ForwardLowering:
         self._norm_vectors(sv, B, HW, C, a["num_groups"])
         sv.route = NormRoute.INFER if (norm == "batch" and not training) else (NormRoute.LAYER if norm == "layer" else NormRoute.GENERIC)
         self._norm_fwd(sv, a, x, out, C, act, training)
+        self._moving_biased(sv, a, C, training)
 
     def _fw_flatten(self, op, bw):
         x = self.val[op.inputs[0]]
@@ -939,7 +989,7 @@ class ForwardLowering:
             return None
         c = cons[0]
         a = c.attrs if c.type == "conv_unit" else None
-        if (a is None or c.inputs[0] is not ot or a["ksize"] != 3 or a.get("transposed") is not None or a.get("general") is not None
+        if (a is None or c.inputs[0] is not ot or a["ksize"] != 3 or a.get("transposed") is not None or a.get("general") is not None or a.get("volume") is not None
                 or a["norm"] not in ("batch", "group", "instance") or (a["norm"] == "batch") != (a["b"] is None)
                 or self.op_lane.get(c) != self.op_lane.get(op) or c in self._lat):
             return None

@@ -202,11 +202,11 @@ def one_hot(s, depth):
 
 
 def concat(values, axis=-1, name=None):
-    """tf.concat along the channel axis of exactly two NHWC tensors (all the zoo needs)."""
+    """tf.concat along the channel axis of exactly two NHWC (or NDHWC) tensors (all the zoo needs)."""
     if len(values) != 2:
         raise NotImplementedError("concat of exactly two tensors")
     a, b = values
-    if axis not in (-1, 3) or a.shape[:-1] != b.shape[:-1]:
+    if axis not in (-1, len(a.shape) - 1) or len(a.shape) not in (4, 5) or a.shape[:-1] != b.shape[:-1]:
         raise ValueError("concat: channel axis only, equal spatial shapes (%s vs %s)" % (a.shape, b.shape))
     kind = KIND_F32 if (a.kind == KIND_F32 and b.kind == KIND_F32) else KIND_ACT
     return get_default_graph().add_op("concat", [a, b], {}, [(a.shape[:-1] + (a.shape[-1] + b.shape[-1],), kind)],
@@ -220,16 +220,31 @@ def random_normal(like, stream):
 
 
 def conv_unit(x, W, b, ksize, norm, norm_vars, act, training, num_groups=None, head=False, name="conv", transposed=None,
-              general=None):
+              general=None, volume=None):
     """conv (SAME, stride 1) -> [+bias] -> [norm] -> act as ONE node (tfwrapper/layers.py:122-135).
     transposed = (kh, kw, sh, sw): tf.nn.conv2d_transpose instead (layers.py:197-258), W is [kh, kw, Cout, Cin] and the output
     is sh x sw times larger.  general = (kh, kw, sh, sw, dh, dw): strided / dilated SAME convolution (conv2D with strides,
     dilated_conv2D, dense_layer as a 1x1 convolution of the flattened input) on the direct kernels of csrc/gconv.hip; the
-    output is ceil(H / sh) x ceil(W / sw)."""
+    output is ceil(H / sh) x ceil(W / sw).  volume = (form, kd, kh, kw, sd, sh, sw) on a 5-D [B, D, H, W, C] input (csrc/conv3d.hip):
+    form "conv" is tf.nn.conv3d with W [kd, kh, kw, Cin, Cout] and output ceil(D / sd) x ceil(H / sh) x ceil(W / sw) (conv3D,
+    layers.py:148-194), form "tconv" tf.nn.conv3d_transpose with W [kd, kh, kw, Cout, Cin] and output D sd x H sh x W sw
+    (transposed_conv3D, layers.py:261-323)."""
     kind = KIND_F32 if head else KIND_ACT
     attrs = dict(W=W, b=b, ksize=int(ksize), norm=norm, norm_vars=norm_vars, act=act, training=training,
-                 num_groups=num_groups, head=head, transposed=transposed, general=general)
-    if transposed is not None:
+                 num_groups=num_groups, head=head, transposed=transposed, general=general, volume=volume)
+    if volume is not None:
+        if len(x.shape) != 5 or len(W.shape) != 5 or volume[0] not in ("conv", "tconv") or transposed is not None or general is not None:
+            raise ValueError("conv_unit: volume = ('conv' | 'tconv', kd, kh, kw, sd, sh, sw) takes a 5-D input and a 5-D filter")
+        if norm not in (None, "batch"):
+            raise NotImplementedError("3-D units take tfnorm.identity or tfnorm.batch_norm, not %r" % (norm,))
+        st = volume[4:7]
+        if volume[0] == "tconv":
+            shape = (x.shape[0],) + tuple(n * s for n, s in zip(x.shape[1:4], st)) + (W.shape[3],)
+        else:
+            shape = (x.shape[0],) + tuple(-(-n // s) for n, s in zip(x.shape[1:4], st)) + (W.shape[4],)
+    elif len(x.shape) == 5:
+        raise ValueError("conv_unit: a 5-D input needs volume= (conv3D / transposed_conv3D), got %r" % (x,))
+    elif transposed is not None:
         kh, kw, sh, sw = transposed
         shape = (x.shape[0], x.shape[1] * sh, x.shape[2] * sw, W.shape[2])
     elif general is not None:
@@ -249,6 +264,37 @@ def max_pool2x2(x):
     """tf.nn.max_pool 2x2 / stride 2 / SAME (tfwrapper/layers.py:18-28)."""
     n, h, w, c = x.shape
     return get_default_graph().add_op("maxpool", [x], {}, [((n, (h + 1) // 2, (w + 1) // 2, c), x.kind)])[0]
+
+
+def max_pool3d(x, window=(2, 2, 2)):
+    """tf.nn.max_pool3d, window = stride = `window` (each entry 1 or 2), SAME (tfwrapper/layers.py:31-41)."""
+    n, d, h, w, c = x.shape
+    pd, ph, pw = (int(v) for v in window)
+    if any(v not in (1, 2) for v in (pd, ph, pw)):
+        raise ValueError("max_pool3d: window entries 1 or 2, got %s" % (window,))
+    return get_default_graph().add_op("max_pool3d", [x], dict(window=(pd, ph, pw)),
+                                      [((n, -(-d // pd), -(-h // ph), -(-w // pw), c), x.kind)], name="maxpool3d")[0]
+
+
+def bilinear_up3d(x, name="ups3d"):
+    """bilinear_upsample3D by 2 (tfwrapper/layers.py:348-376): legacy tf.image.resize_bilinear on the planes, then along D."""
+    n, d, h, w, c = x.shape
+    return get_default_graph().add_op("bilinear_up3d", [x], {}, [((n, 2 * d, 2 * h, 2 * w, c), x.kind)], name=name)[0]
+
+
+def spatial_window3d(x, out_dhw, off, name="window3d"):
+    """out[b, z, y, x] = x[b, z + off_z, y + off_y, x + off_x] inside x, 0 outside: the 5-D centre crop of crop_and_concat
+    (layers.py:609-612) for positive offsets, zero padding for negative ones."""
+    n, d, h, w, c = x.shape
+    return get_default_graph().add_op("spatial_window3d", [x], dict(off=tuple(int(v) for v in off)),
+                                      [((n,) + tuple(int(v) for v in out_dhw) + (c,), x.kind)], name=name)[0]
+
+
+def fold_depth(x):
+    """[B, D, H, W, ...] -> [B, D * H, W, ...]: the same memory seen with one spatial axis fewer (a view, no launch).  The per-pixel
+    cross-entropies and the per-sample Dice sums of tfwrapper.losses do not depend on the fold."""
+    return get_default_graph().add_op("fold_depth", [x], {}, [((x.shape[0], x.shape[1] * x.shape[2]) + tuple(x.shape[3:]), x.kind)],
+                                      name="fold_depth")[0]
 
 
 def spatial_window(x, out_h, out_w, off_y, off_x, name="window"):
@@ -287,12 +333,14 @@ def add_act(a, b, act="identity", name="add"):
 def norm_act(x, norm, norm_vars, act, training, num_groups=None, name="norm"):
     """act(normalisation(x)) as a node of its own: the pre-activation order of identity_residual_unit2D (layers.py:512-518), where
     the normalisation does not follow a convolution."""
+    if len(x.shape) == 5 and norm not in (None, "batch"):
+        raise NotImplementedError("a 5-D tensor takes tfnorm.identity or tfnorm.batch_norm, not %r" % (norm,))
     attrs = dict(norm=norm, norm_vars=norm_vars, act=act, training=training, num_groups=num_groups)
     return get_default_graph().add_op("norm_act", [x], attrs, [(x.shape, x.kind)], name=name)[0]
 
 
 def flatten(x):
-    """tfwrapper/utils.py:16-22 flatten: [B, ...] -> [B, 1, 1, prod(...)] (NHWC memory order kept: a view, no launch); the
+    """tfwrapper/utils.py:16-22 flatten: [B, ...] (4-D or 5-D) -> [B, 1, 1, prod(...)] (NHWC memory order kept: a view, no launch); the
     extra unit axes keep every tensor of the engine four-dimensional."""
     n = x.shape[0]
     f = int(np.prod(x.shape[1:]))
@@ -375,7 +423,19 @@ def _seg_loss_inputs(logits, labels, what):
     """-> (full-resolution fp32 logits [B,H,W,C], u8 labels [B,H,W]).  `labels` is the u8 class-index tensor or G.one_hot of it (the
     kernels fold the one-hot into the u8 read); a level stored at a coarser resolution is summed to full resolution first (aggregate_logits)."""
     if len(logits.shape) == 5:
-        raise NotImplementedError("%s: 3-D (5-D logits) segmentation is not part of this port" % what)
+        # a volume [B, D, H, W, C] with labels G.one_hot of a u8 [B, D, H, W] placeholder (the form the reference's losses take: a
+        # one-hot tensor of the logits' rank): both seen as [B, D * H, W, ..] (fold_depth: a view, no launch).  Any other label form
+        # on 5-D logits stays refused.
+        if labels.kind == KIND_U8 or labels.op is None or labels.op.type != "one_hot":
+            raise NotImplementedError("%s: 3-D (5-D logits) segmentation takes its labels as G.one_hot of the u8 [B, D, H, W] "
+                                      "placeholder; other label forms are not part of this port" % what)
+        if labels.op.attrs["depth"] != logits.shape[4]:
+            raise ValueError("%s: labels are one-hot of depth %d, the logits have %d classes" % (what, labels.op.attrs["depth"], logits.shape[4]))
+        labels = labels.op.inputs[0]
+        if logits.kind != KIND_F32 or labels.kind != KIND_U8 or tuple(labels.shape) != tuple(logits.shape[:4]):
+            raise ValueError("%s: a volume takes fp32 logits [B, D, H, W, C] and G.one_hot of u8 labels [B, D, H, W], got %r / %r"
+                             % (what, logits, labels))
+        logits, labels = fold_depth(logits), fold_depth(labels)
     if len(logits.shape) != 4 or logits.kind != KIND_F32 or not 2 <= logits.shape[3] <= 8:
         raise ValueError("%s: logits must be an fp32 [B, H, W, C] tensor (a logit head) with 2 <= C <= 8, got %r" % (what, logits))
     if labels.kind != KIND_U8 and labels.op is not None and labels.op.type == "one_hot":

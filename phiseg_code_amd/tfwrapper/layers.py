@@ -3,9 +3,11 @@
 Hot-path layers (surface B1): ``conv2D`` (layers.py:94-145), ``averagepool2D`` (44-54),
 ``bilinear_upsample2D`` (336-345), ``global_averagepool2D`` (70-78), ``crop_and_concat`` (586-622),
 ``nearest_neighbour_upsample2D`` (326-333).  Every call adds nodes to ``phiseg_code_amd.graph``; the arithmetic
-runs in hand-written HIP kernels (libphx.so).  Layers that no PHiSeg configuration calls (3-D variants,
-residual units, dense, dilated conv) keep their names and raise NotImplementedError; transposed_conv2D (named by the
-north star) is implemented on direct kernels.
+runs in hand-written HIP kernels (libphx.so).  The layers that no PHiSeg configuration calls are implemented as well, on direct
+kernels: strided / dilated / transposed convolutions, residual units, dense, max pool, pad and crop (csrc/gconv.hip, csrc/tconv.hip),
+and the 3-D family -- ``conv3D``, ``transposed_conv3D``, ``maxpool3D``, ``bilinear_upsample3D`` and the 5-D branch of
+``crop_and_concat`` on NDHWC tensors [B, D, H, W, C] (csrc/conv3d.hip).  3-D units take tfnorm.identity or
+tfnorm.batch_norm; what a layer does not support raises NotImplementedError with the reason.
 """
 import logging
 
@@ -348,6 +350,8 @@ def bilinear_upsample2D(x, name, factor):
 def crop_and_concat(inputs, axis=-1):
     """tfwrapper/layers.py:586-622: the first feature map defines the output size, the others are centre-cropped to it
     (start = (larger - output) // 2) and everything is concatenated along the channel axis."""
+    if len(inputs[0].get_shape().as_list()) == 5:
+        return _crop_and_concat3D(inputs, axis)
     if axis not in (-1, 3):
         raise ValueError("crop_and_concat: channel axis only")
     out_size = inputs[0].get_shape().as_list()[1:3]
@@ -363,14 +367,124 @@ def crop_and_concat(inputs, axis=-1):
     return out
 
 
-def _not_on_hot_path(name):
-    def fn(*args, **kwargs):
-        raise NotImplementedError("%s has zero call sites in phiseg/ (SURVEY.md section 2, out of scope)" % name)
-    fn.__name__ = name
-    return fn
+def _crop_and_concat3D(inputs, axis):
+    """the 5-D branch of crop_and_concat (tfwrapper/layers.py:609-612): centre crop on three axes"""
+    if axis not in (-1, 4):
+        raise ValueError("crop_and_concat: channel axis only")
+    out_size = inputs[0].get_shape().as_list()[1:4]
+    out = inputs[0]
+    for t in inputs[1:]:
+        larger = t.get_shape().as_list()[1:4]
+        if larger != out_size:
+            if any(l < o for l, o in zip(larger, out_size)):
+                raise ValueError("crop_and_concat: %s cannot be cropped to %s" % (larger, out_size))
+            t = G.spatial_window3d(t, out_size, [(l - o) // 2 for l, o in zip(larger, out_size)], name='crop')
+        out = G.concat([out, t], axis=-1)
+    return out
 
 
-maxpool3D = _not_on_hot_path("maxpool3D")
-conv3D = _not_on_hot_path("conv3D")
-transposed_conv3D = _not_on_hot_path("transposed_conv3D")
-bilinear_upsample3D = _not_on_hot_path("bilinear_upsample3D")
+# ---- the 3-D layer family (DESIGN.md section 7h; kernels in csrc/conv3d.hip) -------------------------------------------------------
+def maxpool3D(x, kernel_size=(2, 2, 2), strides=(2, 2, 2), padding="SAME"):
+    """tf.nn.max_pool3d, SAME (tfwrapper/layers.py:31-41): window = stride, each entry 1 or 2 -- 2x2x2 by default, (1, 2, 2) for
+    anisotropic volumes."""
+    if tuple(kernel_size) != tuple(strides) or any(k not in (1, 2) for k in kernel_size) or len(kernel_size) != 3 or padding != "SAME":
+        raise NotImplementedError("maxpool3D: window = stride with entries 1 or 2, SAME")
+    return G.max_pool3d(x, kernel_size)
+
+
+def _volume_unit(x, name, form, kernel_size, num_filters, strides, activation, normalisation, normalise_post_activation, dropout_p,
+                 weight_init, add_bias, kwargs):
+    """What conv3D and transposed_conv3D share: W (and b, kept even in front of batch norm: layers.py:178-181, 307-310) under `name`,
+    conv -> bias -> normalisation -> activation as one unit, or -- normalise_post_activation -- the unit with the activation and no
+    normalisation followed by a normalisation node under the same scope, then dropout."""
+    if normalisation not in tfnorm.KIND:
+        raise ValueError("Unknown normalisation callable %r" % (normalisation,))
+    if activation not in activations.ACT_NAME:
+        raise ValueError("Unknown activation callable %r" % (activation,))
+    kind = tfnorm.KIND[normalisation]
+    if kind not in (None, "batch"):
+        why = {"group": "group_norm2D reshapes a rank-4 tensor and fails on a volume in the reference itself",
+               "instance": "instance_norm2D takes its moments over axes (1, 2) only and misreads a volume in the reference itself",
+               "layer": "layer_norm's default axes (1, 2, 3) leave out the W axis of a volume",
+               "renorm": "batch_renorm on volumes is left for later"}[kind]
+        raise NotImplementedError("%s: %s" % (name, why))
+    shp = x.get_shape().as_list()
+    if len(shp) != 5:
+        raise ValueError("%s: a [B, D, H, W, C] tensor is expected, got %s" % (name, shp))
+    kd, kh, kw = (int(k) for k in kernel_size)
+    cin = shp[4]
+    weight_shape = [kd, kh, kw, cin, num_filters] if form == "conv" else [kd, kh, kw, num_filters, cin]
+    g = G.get_default_graph()
+    training = kwargs.get('training', True)
+    an = activations.ACT_NAME[activation]
+    volume = (form, kd, kh, kw) + tuple(int(s) for s in strides)
+    with g.variable_scope(name):
+        weights = utils.get_weight_variable(weight_shape, name='W', type=weight_init, regularize=True)
+        biases = utils.get_bias_variable([num_filters], name='b') if add_bias else None
+        norm_vars = tfnorm.make_variables(kind, num_filters)
+        # heads (identity normalisation, activation other than relu) keep fp32 storage in the bf16 configuration, as in conv2D
+        head = kind is None and activation is not activations.relu
+        uname = 'conv' if form == "conv" else 'deconv'
+        if normalise_post_activation and kind is not None:
+            op = G.conv_unit(x, weights, biases, kd, None, {}, an, training, head=False, name=uname, volume=volume)
+            op = G.norm_act(op, kind, norm_vars, 'identity', training, name='norm')
+        else:
+            op = G.conv_unit(x, weights, biases, kd, kind, norm_vars, an, training, head=head, name=uname, volume=volume)
+        if dropout_p is not None:
+            op = dropout(op, keep_prob=dropout_p, training=training)
+        return op
+
+
+def conv3D(x,
+           name,
+           kernel_size=(3,3,3),
+           num_filters=32,
+           strides=(1,1,1),
+           activation=STANDARD_NONLINEARITY,
+           normalisation=tfnorm.identity,
+           normalise_post_activation=False,
+           dropout_p=None,
+           padding="SAME",
+           weight_init='he_normal',
+           add_bias=True,
+           **kwargs):
+    """Standard 3-D convolutional layer (tfwrapper/layers.py:148-194): tf.nn.conv3d, SAME -> [bias] -> normalisation -> activation
+    (or activation -> normalisation with normalise_post_activation) [-> dropout].  W is [kd, kh, kw, Cin, num_filters]; unlike conv2D
+    the reference keeps the bias in front of batch norm here (lines 178-181).  kwargs can carry ``training``."""
+    if padding != "SAME":
+        raise NotImplementedError("conv3D: SAME padding only")
+    return _volume_unit(x, name, "conv", kernel_size, num_filters, strides, activation, normalisation, normalise_post_activation,
+                        dropout_p, weight_init, add_bias, kwargs)
+
+
+def transposed_conv3D(bottom,
+                      name,
+                      kernel_size=(4,4,4),
+                      num_filters=32,
+                      strides=(2,2,2),
+                      output_shape=None,
+                      activation=STANDARD_NONLINEARITY,
+                      normalisation=tfnorm.identity,
+                      normalise_post_activation=False,
+                      dropout_p=None,
+                      padding="SAME",
+                      weight_init='he_normal',
+                      add_bias=True,
+                      **kwargs):
+    """Standard 3-D transposed convolution (tfwrapper/layers.py:261-323): tf.nn.conv3d_transpose with a [kd, kh, kw, num_filters,
+    bottom channels] filter, by default up-sampling by 2; -> [bias] -> normalisation -> activation [-> dropout]."""
+    if padding != "SAME":
+        raise NotImplementedError("transposed_conv3D: SAME padding (the reference's default) only")
+    shp = bottom.get_shape().as_list()
+    if output_shape is not None and tuple(output_shape[1:4]) != tuple(n * s for n, s in zip(shp[1:4], strides)):
+        raise NotImplementedError("transposed_conv3D: output_shape other than input * strides")
+    return _volume_unit(bottom, name, "tconv", kernel_size, num_filters, strides, activation, normalisation, normalise_post_activation,
+                        dropout_p, weight_init, add_bias, kwargs)
+
+
+def bilinear_upsample3D(x, name, factor):
+    """tfwrapper/layers.py:348-376: tf.image.resize_bilinear (legacy coordinates) on the (H, W) planes, then along D."""
+    if factor != 2:
+        raise NotImplementedError("hot path: factor 2")
+    with G.get_default_graph().variable_scope(name):
+        return G.bilinear_up3d(x, name="ResizeBilinear")
