@@ -81,9 +81,35 @@ static __device__ unsigned long long* g_phx_blocklog = nullptr;   // debug: per-
             g_phx_blocklog[bi * 4 + 3] = wall_clock64();                                                 \
         }                                                                                                \
     } while (0)
-#define PHX_TRACE(slot)                                                                                  \
+// PHX_TRACE_PUT: a stamp READ earlier (one scalar instruction where it was read, no branch there) and stored here -- the stamps of
+// the forward kernel's prologue, where a branch in front of the first loads would move what is being timed
+#define PHX_TRACE_PUT(slot, cycles)                                                                      \
     do {                                                                                                 \
         if (g_phx_trace && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0)    \
-            g_phx_trace[slot] = __builtin_readcyclecounter();                                            \
+            g_phx_trace[slot] = (cycles);                                                                \
+    } while (0)
+#define PHX_TRACE(slot) PHX_TRACE_PUT(slot, __builtin_readcyclecounter())
+// PHX_TRACE / PHX_BLOCKLOG_END read their buffer's pointer from memory where they stand: a dependent round trip (address, pointer,
+// s_waitcnt vmcnt(0) -- which also waits for every load and store in flight) at each of them, in every block, traced or not.  A
+// kernel whose time is such round trips (k_conv3x3_mfma) loads the two pointers ONCE at its entry, moves them to scalar registers
+// behind its first loads (phx_uniform_ptr) and stamps through PHX_TRACE_TO / PHX_BLOCKLOG_END_TO: a scalar compare per stamp.
+__device__ __forceinline__ unsigned long long* phx_uniform_ptr(unsigned long long v) {
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return reinterpret_cast<unsigned long long*>(((unsigned long long)hi << 32) | lo);
+}
+#define PHX_TRACE_TO(buf, slot, cycles)                                                                  \
+    do {                                                                                                 \
+        if ((buf) != nullptr && threadIdx.x == 0) (buf)[slot] = (cycles);   /* buf: null in every block but (0,0,0) */ \
+    } while (0)
+#define PHX_BLOCKLOG_END_TO(buf)                                                                         \
+    do {                                                                                                 \
+        if ((buf) != nullptr && threadIdx.x == 0) {                                                      \
+            const size_t bi = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;    \
+            (buf)[bi * 4 + 0] = bl_t0;                                                                   \
+            (buf)[bi * 4 + 1] = __builtin_readcyclecounter();                                            \
+            (buf)[bi * 4 + 2] = (unsigned long long)__builtin_amdgcn_s_getreg(63492) |                   \
+                                ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32);            \
+            (buf)[bi * 4 + 3] = wall_clock64();                                                          \
+        }                                                                                                \
     } while (0)
 

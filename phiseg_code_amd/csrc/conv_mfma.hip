@@ -241,6 +241,37 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (NA > 8 && DUAL)) ? 1 : 2) voi
                                                          unsigned short* __restrict__ y, const float* __restrict__ bias,
                                                          int act, float* __restrict__ stats_partial, int B, int H, int W,
                                                          int K, int N, MTile g, float* __restrict__ ws, EpiOpts bws, XForm xf, Dual du) {
+    // Order of the prologue.  A small-map block is a chain of dependent memory round trips, and the first of them -- the first chunk's
+    // filter slab and input patch -- used to start only behind the whole staging plan: 350 - 860 instructions of a block that, on the
+    // 2 x 2 and 4 x 4 levels, runs ONE chunk and exits.  LOADS FIRST (the default): the slab loads, which need only the channel block
+    // and threadIdx, go out right behind the block decode; every patch piece is loaded as soon as its own offset is known; and what no
+    // load depends on (LDS offsets, operand offsets, the accumulators' zeros) is computed behind the issued loads.  No load sits in a
+    // branch or behind a select of loaded values: a piece outside the patch keeps offset 0xffffffff and the range check returns zeros.
+    // The values staged, the MFMA order and the epilogues are the same in both orders.
+#ifndef PHX_CONV_LOADS_FIRST   // 0: the plan-first order (dev A/B: tools/build_variant.sh NAME -DPHX_CONV_LOADS_FIRST=0)
+#define PHX_CONV_LOADS_FIRST 1
+#endif
+    // (Five instantiations keep the plan-first order: reordered, the 128-channel blocks of the 512-pixel tiles and the 64-channel
+    // non-split-K blocks of the 4 x 4 x 16 / 2 x 2 x 64 tiles -- all at 256 registers already -- spill 24 - 88 bytes per lane to scratch.)
+    constexpr bool LF = PHX_CONV_LOADS_FIRST != 0 && BN != 128 && !(BN == 64 && NA == 16 && !SPLITK && !DUAL);
+    // The debug buffers' pointers (stamps of block 0, per-block log) belong to the same chain: PHX_TRACE / PHX_BLOCKLOG_* load the
+    // pointer where they stand and wait for it -- two round trips in front of the first loads, five more in the bf16 epilogue and one
+    // at the end of every block, with nothing being traced.  LOADS FIRST loads both pointers here and looks at them behind the issued
+    // loads, from scalar registers (conv_common.h: phx_uniform_ptr).
+    const unsigned long long trv = LF ? (unsigned long long)g_phx_trace : 0ull, blv = LF ? (unsigned long long)g_phx_blocklog : 0ull;
+    if constexpr (LF) asm volatile("" ::: "memory");      // (the two loads stay HERE: without it they sink to their first use, behind the prologue)
+    const unsigned long long t_in = __builtin_readcyclecounter();      // entry stamp (one scalar instruction; stored behind the loads)
+    unsigned long long *trc = nullptr, *blg = nullptr;
+#define CONV_TRACE(slot)                                                            \
+    do {                                                                            \
+        if constexpr (LF) PHX_TRACE_TO(trc, slot, __builtin_readcyclecounter());    \
+        else PHX_TRACE(slot);                                                       \
+    } while (0)
+#define CONV_BLOCKLOG_END()                                \
+    do {                                                   \
+        if constexpr (LF) PHX_BLOCKLOG_END_TO(blg);        \
+        else PHX_BLOCKLOG_END();                           \
+    } while (0)
     constexpr int NJ = BN / 32;
     constexpr int NT = NW * 64;                            // threads; the tile has NT pixels
     constexpr int NB = (9 * BN * 4 + NT - 1) / NT;        // filter-slab pieces per thread
@@ -258,36 +289,46 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (NA > 8 && DUAL)) ? 1 : 2) voi
     // own L2: the N / BN channel blocks of a tile get ids 8 apart -- same XCD, dispatched back to back -- so the input
     // patch they all read comes from HBM once; the tiles of an XCD are a contiguous band of the launch (phx_band8), so the halos
     // of neighbouring tiles meet in that L2 too.  (Placement only affects speed, never results.)
+    // (loads first: the decode stands in front of the first load, so its divisions are unsigned -- every operand is a count; a signed
+    // division carries eight more scalar instructions of sign handling)
+    using DI = std::conditional_t<LF, unsigned, int>;
     int tile_id, cob;
     {
-        const int ncob = N / BN, ntl = g.tiles_x * g.tiles_y * g.tiles_b;
-        const int id = blockIdx.x, full = (ntl >> 3) * 8 * ncob;
+        const DI ncob = (DI)N / BN, ntl = g.tiles_x * g.tiles_y * g.tiles_b;
+        const DI id = blockIdx.x, full = (ntl >> 3) * 8 * ncob;
         if (id < full) {
-            const int grp = id / (8 * ncob), r = id - grp * 8 * ncob;
-            tile_id = phx_band8(grp * 8 + (r & 7), ntl);           // (XCD bands: phx_common.h)
-            cob = r >> 3;
+            const DI grp = id / (8 * ncob), r = id - grp * 8 * ncob;
+            tile_id = phx_band8((int)(grp * 8 + (r & 7)), (int)ntl);           // (XCD bands: phx_common.h)
+            cob = (int)(r >> 3);
         } else {
-            const int rem = ntl & 7, r = id - full;
-            tile_id = (ntl & ~7) + r % rem;
-            cob = r / rem;
+            const DI rem = ntl & 7, r = id - full;
+            tile_id = (int)((ntl & ~(DI)7) + r % rem);
+            cob = (int)(r / rem);
         }
     }
-    int t = tile_id;
-    const int tx0 = (t % g.tiles_x) << g.tws; t /= g.tiles_x;
-    const int ty0 = (t % g.tiles_y) << g.ths; t /= g.tiles_y;
-    const int b0 = t * g.tb;
+    int tx0, ty0, b0;
+    auto tile_origin = [&]() {
+        DI t = tile_id;
+        tx0 = (t % g.tiles_x) << g.tws; t /= g.tiles_x;
+        ty0 = (t % g.tiles_y) << g.ths; t /= g.tiles_y;
+        b0 = t * g.tb;
+    };
+    if constexpr (!LF) tile_origin();
     const int n0 = cob * BN;
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int l31 = lane & 31, khalf = lane >> 5;
-    int aoff[2];
+    int aoff[2], boff;
+    auto operand_offsets = [&]() {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int m = wave * 64 + i * 32 + l31;
-        const int lx = m & (tw - 1), ly = (m >> g.tws) & (th - 1), lb = m >> (g.tws + g.ths);
-        aoff[i] = (FAST16 ? (lb * ph + ly) * pitch : lb * g.ipitch + ly * pitch) + lx * ROWB + khalf * 16;
-    }
-    const int boff = l31 * ROWB + khalf * 16;
+        for (int i = 0; i < 2; ++i) {
+            const int m = wave * 64 + i * 32 + l31;
+            const int lx = m & (tw - 1), ly = (m >> g.tws) & (th - 1), lb = m >> (g.tws + g.ths);
+            aoff[i] = (FAST16 ? (lb * ph + ly) * pitch : lb * g.ipitch + ly * pitch) + lx * ROWB + khalf * 16;
+        }
+        boff = l31 * ROWB + khalf * 16;
+    };
+    if constexpr (!LF) operand_offsets();
 
     // staging plan: BYTE offsets (without the channel-chunk term) of this thread's 16-byte pieces for raw buffer loads;
     // 0xffffffff = outside the image / batch / slab -> the buffer range check returns zeros, so the prefetch is
@@ -296,32 +337,57 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (NA > 8 && DUAL)) ? 1 : 2) voi
     unsigned ga2[DUAL ? NA : 1];                 // DUAL: the same pieces in du.x2 (pixel stride K - K1)
     unsigned sa[FAST16 ? 1 : NA];                // small-map tiles: LDS byte offset of the piece's pixel (padded pitches, see mtile_magic)
     const int K1 = (DUAL && du.x2 != nullptr) ? du.K1 : K;      // channels (= pixel stride) of x
-#pragma unroll
-    for (int it = 0; it < NA; ++it) {
-        const int i = threadIdx.x + it * NT;
+    // piece `it` of thread `tid`: global byte offsets in x / du.x2 and the LDS offset of its pixel (whatever a caller does not use is
+    // dead code).  Branch-free: the coordinates of a piece outside the patch (pp >= npatch) are garbage below 2^21 and masked by `in`.
+    auto piece_plan = [&](int tid, int it, unsigned* off_out, unsigned* off2_out, unsigned* so_out) {
+        const int i = tid + it * NT;
         const int q = i & 3, pp = i >> 2;
-        ga[it] = 0xffffffffu;
-        if constexpr (DUAL) ga2[it] = 0xffffffffu;
-        if constexpr (!FAST16) sa[it] = 0;
-        if (pp < npatch) {
-            // 16-wide tiles: the patch is 18 wide -> compile-time divisors (runtime division costs ~40 instructions)
-            int px, py, pb;
-            if constexpr (FAST16) { px = pp % 18; py = pp / 18; pb = 0; }
-            else patch_coords(g, pp, pw, ph, &px, &py, &pb);
-            if constexpr (!FAST16) sa[it] = (unsigned)(pb * g.ipitch + py * g.rpitch + px * ROWB);
-            const int gx = tx0 + px - 1, gy = ty0 + py - 1, gbi = b0 + pb;
-            const bool in = (unsigned)gx < (unsigned)W && (unsigned)gy < (unsigned)H && gbi < B;
-            unsigned off, off2 = 0;
-            if constexpr (FAST16) {
-                off = (unsigned)((((gbi * H + gy) * W + gx) * K1 + q * 8) * 2);
-                if constexpr (DUAL) off2 = (unsigned)((((gbi * H + gy) * W + gx) * (K - K1) + q * 8) * 2);
-            } else {                                           // small maps: B * H * W < 2^24 (checked by the launcher)
-                const unsigned pix = __umul24(__umul24((unsigned)gbi, (unsigned)H) + gy, (unsigned)W) + gx;
-                off = (__umul24(pix, (unsigned)K1) + q * 8) * 2;
-                if constexpr (DUAL) off2 = (__umul24(pix, (unsigned)(K - K1)) + q * 8) * 2;
+        // 16-wide tiles: the patch is 18 wide -> compile-time divisors (runtime division costs ~40 instructions)
+        int px, py, pb;
+        if constexpr (FAST16) { px = pp % 18; py = pp / 18; pb = 0; }
+        else patch_coords(g, pp, pw, ph, &px, &py, &pb);
+        *so_out = FAST16 ? 0u : (unsigned)(pb * g.ipitch + py * g.rpitch + px * ROWB);
+        const int gx = tx0 + px - 1, gy = ty0 + py - 1, gbi = b0 + pb;
+        const bool in = pp < npatch && (unsigned)gx < (unsigned)W && (unsigned)gy < (unsigned)H && gbi < B;
+        unsigned off, off2 = 0;
+        if constexpr (FAST16) {
+            off = (unsigned)((((gbi * H + gy) * W + gx) * K1 + q * 8) * 2);
+            if constexpr (DUAL) off2 = (unsigned)((((gbi * H + gy) * W + gx) * (K - K1) + q * 8) * 2);
+        } else {                                           // small maps: B * H * W < 2^24 (checked by the launcher)
+            const unsigned pix = __umul24(__umul24((unsigned)gbi, (unsigned)H) + gy, (unsigned)W) + gx;
+            off = (__umul24(pix, (unsigned)K1) + q * 8) * 2;
+            if constexpr (DUAL) off2 = (__umul24(pix, (unsigned)(K - K1)) + q * 8) * 2;
+        }
+        *off_out = in ? off : 0xffffffffu;
+        *off2_out = in ? off2 : 0xffffffffu;
+    };
+    if constexpr (!LF) {
+#pragma unroll
+        for (int it = 0; it < NA; ++it) {
+            const int i = threadIdx.x + it * NT;
+            const int q = i & 3, pp = i >> 2;
+            ga[it] = 0xffffffffu;
+            if constexpr (DUAL) ga2[it] = 0xffffffffu;
+            if constexpr (!FAST16) sa[it] = 0;
+            if (pp < npatch) {
+                int px, py, pb;
+                if constexpr (FAST16) { px = pp % 18; py = pp / 18; pb = 0; }
+                else patch_coords(g, pp, pw, ph, &px, &py, &pb);
+                if constexpr (!FAST16) sa[it] = (unsigned)(pb * g.ipitch + py * g.rpitch + px * ROWB);
+                const int gx = tx0 + px - 1, gy = ty0 + py - 1, gbi = b0 + pb;
+                const bool in = (unsigned)gx < (unsigned)W && (unsigned)gy < (unsigned)H && gbi < B;
+                unsigned off, off2 = 0;
+                if constexpr (FAST16) {
+                    off = (unsigned)((((gbi * H + gy) * W + gx) * K1 + q * 8) * 2);
+                    if constexpr (DUAL) off2 = (unsigned)((((gbi * H + gy) * W + gx) * (K - K1) + q * 8) * 2);
+                } else {
+                    const unsigned pix = __umul24(__umul24((unsigned)gbi, (unsigned)H) + gy, (unsigned)W) + gx;
+                    off = (__umul24(pix, (unsigned)K1) + q * 8) * 2;
+                    if constexpr (DUAL) off2 = (__umul24(pix, (unsigned)(K - K1)) + q * 8) * 2;
+                }
+                ga[it] = in ? off : 0xffffffffu;
+                if constexpr (DUAL) ga2[it] = in ? off2 : 0xffffffffu;
             }
-            ga[it] = in ? off : 0xffffffffu;
-            if constexpr (DUAL) ga2[it] = in ? off2 : 0xffffffffu;
         }
     }
     // filter-slab pieces: piece `it` of a thread lies it * 64 slab rows further on, i.e. a fixed byte stride -> one VGPR
@@ -337,9 +403,65 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (NA > 8 && DUAL)) ? 1 : 2) voi
     static_assert(NT / 4 % BN == 0, "slab piece stride must be whole taps");
     const int gbs = (NT / 4 / BN) * N * 64;
     const int gcs = 9 * N * 64;                   // bytes per 32-channel chunk of the packed filter
+    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)wpk, 0, (int)(9u * N * K * 2u), 0x00020000);
+    // this block's run of 32-channel chunks [cbeg, cend)
+    int cbeg = 0, cend = K;
+    if constexpr (SPLITK) {
+        const int per = ((DI)K / KC + gridDim.z - 1) / gridDim.z;
+        cbeg = blockIdx.z * per * KC;
+        cend = min(K, cbeg + per * KC);
+    }
+    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+    u32x4 ra[NA], rb[NB];
+    unsigned long long t_slab = 0, t_issued = 0;
+    if constexpr (LF && !(PHX_ABLATE & 1)) {
+        // (1) the first chunk's filter slab
+#pragma unroll
+        for (int it = 0; it < NB; ++it)
+            rb[it] = __builtin_amdgcn_raw_buffer_load_b128(rsw, it == NB - 1 ? gbl : gb0, (cbeg >> 5) * gcs + it * gbs, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        t_slab = __builtin_readcyclecounter();
+        // (2) the first chunk's input patch, piece by piece: offset, then load.  DUAL: the chunk's tensor is a scalar choice, made on
+        // the descriptor and the offset -- one load, no branch
+        tile_origin();
+        const bool second = DUAL && cbeg >= K1;
+        const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)((DUAL && second) ? du.x2 : x), 0, (int)((unsigned)B * H * W * (unsigned)(second ? K - K1 : K1) * 2u), 0x00020000);
+        const int so1 = (second ? cbeg - K1 : cbeg) * 2;
+#pragma unroll
+        for (int it = 0; it < NA; ++it) {
+            unsigned off, off2, so;
+            piece_plan(threadIdx.x, it, &off, &off2, &so);
+            ga[it] = off;
+            if constexpr (DUAL) ga2[it] = off2;
+            ra[it] = __builtin_amdgcn_raw_buffer_load_b128(rs1, (DUAL && second) ? off2 : off, so1, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        t_issued = __builtin_readcyclecounter();
+        // (3) behind the issued loads: what only the staging stores, the operand reads and the MFMAs use.  (The LDS offsets come from
+        // a second evaluation of the piece's coordinates on a laundered thread index: shared with (2), they would either be computed
+        // in front of the loads or keep three more registers per piece alive across them.)
+        if constexpr (!FAST16) {
+            int tid2 = threadIdx.x;
+            asm volatile("" : "+v"(tid2));
+#pragma unroll
+            for (int it = 0; it < NA; ++it) {
+                unsigned off, off2;
+                piece_plan(tid2, it, &off, &off2, &sa[it]);
+            }
+        } else sa[0] = 0;
+        operand_offsets();
+    } else if constexpr (LF) {                   // (dev ablation: no global loads)
+        tile_origin();
+#pragma unroll
+        for (int it = 0; it < NA; ++it) {
+            unsigned off2;
+            piece_plan(threadIdx.x, it, &ga[it], DUAL ? &ga2[DUAL ? it : 0] : &off2, &sa[FAST16 ? 0 : it]);
+        }
+        operand_offsets();
+    }
     const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)((unsigned)B * H * W * K1 * 2u), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsx2 = __builtin_amdgcn_make_buffer_rsrc((void*)(DUAL ? du.x2 : x), 0, DUAL ? (int)((unsigned)B * H * W * (K - K1) * 2u) : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)wpk, 0, (int)(9u * N * K * 2u), 0x00020000);
 
     f32x16 acc[2][NJ];
 #pragma unroll
@@ -349,10 +471,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (NA > 8 && DUAL)) ? 1 : 2) voi
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    PHX_BLOCKLOG_BEGIN();
-    PHX_TRACE(0);
-    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-    u32x4 ra[NA], rb[NB];
+    const unsigned long long bl_t0 = LF ? t_in : (g_phx_blocklog ? __builtin_readcyclecounter() : 0ull);      // (plan first: PHX_BLOCKLOG_BEGIN)
+    if constexpr (!LF) { PHX_TRACE_PUT(10, t_in); PHX_TRACE(0); }
     // piece `idx` (input-patch pieces first, then filter-slab pieces) of the chunk starting at channel c0
     auto prefetch_piece = [&](auto idxc, int c0) {
         constexpr int idx = decltype(idxc)::value;
@@ -366,14 +486,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (NA > 8 && DUAL)) ? 1 : 2) voi
         else if constexpr (idx < NA + NB)
             rb[idx - NA] = __builtin_amdgcn_raw_buffer_load_b128(rsw, idx - NA == NB - 1 ? gbl : gb0, (c0 >> 5) * gcs + (idx - NA) * gbs, 0);
     };
-    // this block's run of 32-channel chunks [cbeg, cend)
-    int cbeg = 0, cend = K;
-    if constexpr (SPLITK) {
-        const int per = (K / KC + gridDim.z - 1) / gridDim.z;
-        cbeg = blockIdx.z * per * KC;
-        cend = min(K, cbeg + per * KC);
-    }
-    {
+    if constexpr (!LF) {
         auto all = [&](auto self, auto idxc) {
             constexpr int idx = decltype(idxc)::value;
             if constexpr (idx < NA + NB) {
@@ -382,8 +495,12 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (NA > 8 && DUAL)) ? 1 : 2) voi
             }
         };
         all(all, std::integral_constant<int, 0>());
+        PHX_TRACE(1);
+    } else {                                     // slot 10: entry; slot 0: slab loads issued; slot 1: every load of the first chunk issued
+        blg = phx_uniform_ptr(blv);
+        trc = (blockIdx.x | blockIdx.y | blockIdx.z) == 0 ? phx_uniform_ptr(trv) : nullptr;
+        PHX_TRACE_TO(trc, 10, t_in); PHX_TRACE_TO(trc, 0, t_slab); PHX_TRACE_TO(trc, 1, t_issued);
     }
-    PHX_TRACE(1);
     // one 32-channel chunk: registers -> LDS, then 18 (tap, k-step) groups of 2 x NJ MFMAs; with PF the global loads of the
     // NEXT chunk are issued one or two per group, so the texture-address unit (64 B/clk: ~1 K cycles per chunk for the four
     // waves) works underneath the matrix pipe instead of in a phase of its own.
@@ -394,7 +511,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (NA > 8 && DUAL)) ? 1 : 2) voi
     auto chunk = [&](int ccur, int cnext, auto pfc, bool tr) {   // ccur: first channel of the chunk in registers; cnext: of the chunk to prefetch
         constexpr bool PF = decltype(pfc)::value;
         __syncthreads();                         // every wave is done reading the previous chunk / epilogue tile from LDS
-        if (tr) PHX_TRACE(2);
+        if (tr) CONV_TRACE(2);
 #pragma unroll
         for (int it = 0; it < NA; ++it) {
             const int i = threadIdx.x + it * NT;
@@ -408,7 +525,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (NA > 8 && DUAL)) ? 1 : 2) voi
             if (!(PHX_ABLATE & 2) && i < 9 * BN * 4) *reinterpret_cast<u32x4*>(sB + (i >> 2) * ROWB + (i & 3) * 16) = rb[it];
         }
         __syncthreads();
-        if (tr) PHX_TRACE(3);
+        if (tr) CONV_TRACE(3);
         // software pipeline, pinned with sched_barrier: the operand reads of group gi+1 and this group's global loads are
         // issued before the MFMAs of group gi (fragment registers double-buffered by group parity)
         // (NJ = 4 keeps a single fragment set -- 128 accumulator registers leave no room for two; its 8 MFMAs per group
@@ -457,7 +574,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (NA > 8 && DUAL)) ? 1 : 2) voi
             }
         };
         group(group, std::integral_constant<int, 0>());
-        if (tr) PHX_TRACE(4);
+        if (tr) CONV_TRACE(4);
     };
     const int odd = lane & 1;
     // Epilogue tile [pixel][BN] bf16 in LDS.  32 / 64-channel blocks: DENSE rows -- a lane group of the 16-byte read-back covers all 16
@@ -470,8 +587,9 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (NA > 8 && DUAL)) ? 1 : 2) voi
     {
         const int cx0 = tx0, cy0 = ty0, cb0 = b0;
         const bool tr0 = true;
-        for (int c0 = cbeg; c0 + KC < cend; c0 += KC) chunk(c0, c0 + KC, std::true_type(), c0 == KC);
-        chunk(cend - KC, 0, std::false_type(), K == 2 * KC);
+        // (stamps 2 - 4: the block's FIRST chunk -- a split-K block of the 2 x 2 / 4 x 4 levels has no other; plan first: the second)
+        for (int c0 = cbeg; c0 + KC < cend; c0 += KC) chunk(c0, c0 + KC, std::true_type(), LF ? c0 == cbeg : c0 == KC);
+        chunk(cend - KC, 0, std::false_type(), LF ? cend - KC == cbeg : K == 2 * KC);
         if constexpr (FGN) {
             constexpr int OROWG = BN * 2, OSWZG = BN == 64 ? 64 : 0;      // the epilogue tile of the standard path (dense, swizzled)
             const int psh = g.tws + g.ths;                   // log2(pixels per sample)
@@ -614,7 +732,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (NA > 8 && DUAL)) ? 1 : 2) voi
                             *reinterpret_cast<const uint4*>(smem + m * OROWG + ((q * 16) ^ ((m & 1) ? OSWZG : 0)));
                 }
             }
-            PHX_BLOCKLOG_END();
+            CONV_BLOCKLOG_END();
             return;
         }
         if constexpr (SPLITK) {
@@ -633,14 +751,15 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (NA > 8 && DUAL)) ? 1 : 2) voi
                         for (int j = 0; j < NJ; ++j) wr[j * 32] = acc[i][j][r];
                     }
                 }
-            PHX_BLOCKLOG_END();
+            if constexpr (LF) CONV_TRACE(6);
+            CONV_BLOCKLOG_END();
             return;
         }
 
         // epilogue: C layout col = lane&31 (channel), row = (r&3) + 8*(r>>2) + 4*(lane>>5) (pixel).  The tile is transposed
         // through LDS ([pixel][BN] bf16, 16-byte padded rows) so that global stores are 16 bytes per lane, 128 contiguous
         // bytes per pixel, instead of 2-byte scattered stores.
-        if (tr0) PHX_TRACE(5);
+        if (tr0) CONV_TRACE(5);
         // (statistics on packed fp32 pairs, the LDS word of a lane pair by one v_perm_b32: 8 instead of 17 VALU instructions per word)
         typedef __attribute__((ext_vector_type(2))) float f32x2_t;
         f32x2_t s1v[NJ], s2v[NJ];
@@ -649,7 +768,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (NA > 8 && DUAL)) ? 1 : 2) voi
         const bool do_stats = stats_partial != nullptr;
         const unsigned psel = odd ? 0x03020706u : 0x05040100u;       // even lane: {own lo, neighbour lo}; odd: {neighbour hi, own hi}
         __syncthreads();                             // all MFMA operand reads of the last chunk are done
-        if (tr0) PHX_TRACE(7);
+        if (tr0) CONV_TRACE(7);
         if constexpr (BIASACT) {                     // rare (no-norm layers): its own instantiation, so that the softplus
 #pragma unroll                                       // code costs the common kernels neither registers nor issue slots
             for (int j = 0; j < NJ; ++j) {
@@ -705,9 +824,9 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (NA > 8 && DUAL)) ? 1 : 2) voi
                     for (int j = 0; j < NJ; ++j)
                         *reinterpret_cast<unsigned*>(lw + (i * 32 + ((2 * rp) & 3) + 8 * ((2 * rp) >> 2)) * OROW + ((j * 64) ^ (odd ? OSWZ : 0))) =
                             pack_pair(i, j, 2 * rp, 1.f, 1.f);
-            if (tr0) PHX_TRACE(8);
+            if (tr0) CONV_TRACE(8);
             __syncthreads();
-            if (tr0) PHX_TRACE(9);
+            if (tr0) CONV_TRACE(9);
             const int mt = threadIdx.x / PPP, q = threadIdx.x % PPP;          // piece it: pixel mt + it * (NT / PPP)
             const unsigned char* lr = smem + mt * OROW + ((q * 16) ^ ((mt & 1) ? OSWZ : 0));      // (NT / PPP is even: row parity = mt & 1)
             // (dual destination: the piece's eight channels lie in y (row length N1) or in du.y2 (row length N - N1))
@@ -744,9 +863,9 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (NA > 8 && DUAL)) ? 1 : 2) voi
                     for (int j = 0; j < NJ; ++j)
                         *reinterpret_cast<unsigned*>(smem + mrow * OROW + (((j * 32 + (l31_o & ~1)) * 2) ^ (odd_o ? OSWZ : 0))) = pack_pair(i, j, r0, f0, f1);
                 }
-            if (tr0) PHX_TRACE(8);
+            if (tr0) CONV_TRACE(8);
             __syncthreads();
-            if (tr0) PHX_TRACE(9);
+            if (tr0) CONV_TRACE(9);
 #pragma unroll
             for (int it = 0; it < PPP; ++it) {       // NT pixels * PPP pieces / NT threads
                 const int i = tid_o + it * NT;
@@ -766,7 +885,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (NA > 8 && DUAL)) ? 1 : 2) voi
                 }
             }
         }
-        if (tr0) PHX_TRACE(6);
+        if (tr0) CONV_TRACE(6);
         if (stats_partial) {
             __syncthreads();
             float* red = reinterpret_cast<float*>(smem);      // [NW waves][2][BN]
@@ -791,7 +910,9 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (NA > 8 && DUAL)) ? 1 : 2) voi
             }
         }
     }
-    PHX_BLOCKLOG_END();
+    CONV_BLOCKLOG_END();
+#undef CONV_TRACE
+#undef CONV_BLOCKLOG_END
 }
 
 // y[pix][n] = bf16(act(sum_z ws[z][pix][n] + bias[n])), four channels per thread
