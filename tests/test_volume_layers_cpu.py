@@ -173,6 +173,50 @@ def test_oracle_agrees_with_tf1_ops_where_they_overlap():
     assert V.same_pads(7, 3, 2) == (4, 1, 1) and V.same_pads(6, 3, 2) == (3, 0, 1) and V.same_pads(5, 2, 1) == (5, 0, 1)
 
 
+@pytest.mark.parametrize("case", [
+    (2, 3, 4, 5, 3, 4, (4, 4, 4), (2, 2, 2)), (1, 2, 3, 4, 2, 3, (3, 3, 3), (1, 2, 2)), (1, 3, 2, 3, 4, 2, (5, 3, 4), (3, 1, 2)),
+    (2, 3, 2, 4, 3, 2, (1, 1, 1), (2, 2, 2)), (1, 2, 3, 3, 2, 3, (2, 1, 3), (3, 2, 2)), (1, 2, 3, 2, 3, 2, (1, 2, 1), (2, 3, 2)),
+])
+def test_oracle_conv3d_transpose_is_the_input_gradient_of_conv3d(case):
+    """The definition of tf.nn.conv3d_transpose (the 3-D twin of test_tconv.py's 2-D test): V.conv3d_transpose_same(x, w, s) is the
+    gradient, contracted with x, of the stride-s SAME convolution V.conv3d_same(z, w, s) with respect to its input z of extent in * s,
+    the filter [kd, kh, kw, Cout, Cin] read as DHWIO.  The last three geometries have k < s on one or more axes."""
+    B, D, H, W, Cin, Cout, k, s = case
+    rng = np.random.default_rng(0)
+    x = _t(rng.standard_normal((B, D, H, W, Cin)))
+    w = _t(rng.standard_normal(tuple(k) + (Cout, Cin)))
+    z = torch.zeros(B, D * s[0], H * s[1], W * s[2], Cout, dtype=torch.float64, requires_grad=True)
+    y = V.conv3d_same(z, w, s)
+    assert y.shape == x.shape
+    (y * x).sum().backward()
+    got = V.conv3d_transpose_same(x, w, s)
+    assert got.shape == z.shape
+    np.testing.assert_allclose(got.numpy(), z.grad.numpy(), rtol=1e-12, atol=1e-12)
+
+
+@pytest.mark.parametrize("k,s", [((3, 3, 3), (1, 1, 1)), ((3, 3, 3), (2, 2, 2)), ((2, 2, 2), (1, 2, 3)), ((1, 1, 1), (2, 2, 2))])
+def test_impulse_helpers_restate_the_oracle_exactly(k, s):
+    """V.impulse_conv3d_same / _adjoint (np.pad and slicing, no convolution) against the oracle under the same one-hot filter: the
+    padded shift is exact, and the adjoint is the oracle's input gradient and its transposed convolution."""
+    rng = np.random.default_rng(1)
+    x = rng.standard_normal((1, 4, 5, 7, 3))
+    o = [V.same_pads(n, k[i], s[i])[0] for i, n in enumerate((4, 5, 7))]
+    dy = rng.standard_normal((1, *o, 5))
+    xs = rng.standard_normal((1, 4, 5, 7, 5))
+    for t, tap in enumerate(np.ndindex(*k)):
+        a, b = t % 3, (2 * t + 1) % 5
+        w = torch.zeros(tuple(k) + (3, 5), dtype=torch.float64)
+        w[tap][a, b] = 1.0
+        z = _t(x).requires_grad_(True)
+        y = V.conv3d_same(z, w, s)
+        assert np.array_equal(y.detach().numpy() + 0.0, V.impulse_conv3d_same(x, k, s, tap, a, b, 5)), tap
+        (y * _t(dy)).sum().backward()
+        assert np.array_equal(z.grad.numpy() + 0.0, V.impulse_conv3d_same_adjoint(dy, (4, 5, 7), k, s, tap, a, b, 3)), tap
+        big = (4 * s[0], 5 * s[1], 7 * s[2])                                   # transposed: filter [.., Cout = 3, Cin = 5]
+        up = V.conv3d_transpose_same(_t(xs), w, s)
+        assert np.array_equal(up.numpy() + 0.0, V.impulse_conv3d_same_adjoint(xs, big, k, s, tap, a, b, 3)), tap
+
+
 def test_biased_moving_variance_oracle():
     x = _t(RNG.standard_normal((2, 3, 4, 5, 6)))
     y, mean, var = V.batch_norm_train_5d(x, torch.ones(6, dtype=torch.float64), torch.zeros(6, dtype=torch.float64))

@@ -38,6 +38,35 @@ def conv3d_transpose_same(x, w_dhwoi, strides=(2, 2, 2)):
     return full[tuple(sl)].permute(0, 2, 3, 4, 1)
 
 
+def impulse_conv3d_same(x, k, strides, tap, a, b, cout):
+    """conv3D with the one-hot filter w[tap][a][b] = 1, no bias, no activation, WITHOUT a convolution (numpy, np.pad and slicing only):
+    output channel b is input channel a zero-padded by the SAME rule, shifted by tap = (tz, ty, tx) and strided -- out[o] =
+    padded[o s + tap] -- and every other output channel is zero.  x [B, D, H, W, Cin] -> [B, Do, Ho, Wo, cout], exact in any dtype."""
+    import numpy as np
+    pads = [same_pads(x.shape[1 + i], k[i], strides[i]) for i in range(3)]
+    xp = np.pad(x[..., a], [(0, 0)] + [(p[1], p[2]) for p in pads])
+    out = np.zeros((x.shape[0],) + tuple(p[0] for p in pads) + (cout,), dtype=x.dtype)
+    sl = tuple(slice(tap[i], tap[i] + (pads[i][0] - 1) * strides[i] + 1, strides[i]) for i in range(3))
+    out[..., b] = xp[(slice(None),) + sl]
+    return out
+
+
+def impulse_conv3d_same_adjoint(dy, big_dhw, k, strides, tap, a, b, ca):
+    """The adjoint of impulse_conv3d_same, by slicing only: channel b of dy [B, Do, Ho, Wo, Cb] (Do = ceil(big / s)) is placed at
+    o s + tap - before on channel a of a zero tensor [B, *big_dhw, ca]; what falls into the SAME padding is dropped.  This is the data
+    gradient of conv3D under the one-hot filter w[tap][a][b] = 1, and -- conv3d_transpose being the input gradient of the stride-s SAME
+    convolution on its own output extent in * s -- transposed_conv3D's forward pass under w_dhwoi[tap][a][b] = 1."""
+    import numpy as np
+    pads = [same_pads(big_dhw[i], k[i], strides[i]) for i in range(3)]
+    assert tuple(dy.shape[1:4]) == tuple(p[0] for p in pads)
+    xp = np.zeros((dy.shape[0],) + tuple(big_dhw[i] + pads[i][1] + pads[i][2] for i in range(3)), dtype=dy.dtype)
+    sl = tuple(slice(tap[i], tap[i] + (pads[i][0] - 1) * strides[i] + 1, strides[i]) for i in range(3))
+    xp[(slice(None),) + sl] = dy[..., b]
+    out = np.zeros((dy.shape[0],) + tuple(big_dhw) + (ca,), dtype=dy.dtype)
+    out[..., a] = xp[(slice(None),) + tuple(slice(pads[i][1], pads[i][1] + big_dhw[i]) for i in range(3))]
+    return out
+
+
 def bias_add(x, b):
     return x + b.reshape(1, 1, 1, 1, -1)
 
