@@ -10,7 +10,7 @@ FAIL and the next check runs; anything else (a HIP error, an unexpected PhxError
 ends the process with a non-zero status at once: nothing more is started on the GPU.  Nothing is retried.
 
 Which check reaches which deterministic branch:
-  losses_opt.hip  k_residual_ce fixed point / k_reduce_loss_parts   residual_ce[...]
+  losses_opt.hip  k_residual_ce fixed point / k_reduce_loss_parts   residual_ce[...], residual_ce_contract[...]
                   phx_kl_diag_gauss (one block)                      kl_and_adam, kl_multi[...] (its per-level launches)
                   phx_kl_diag_gauss_multi (one block per level)      kl_multi[...]
   norm.hip        phx_norm_stats chunk = P                           norm_stats_one_block[...], norm_fwd_bwd[...], bn_small[...]
@@ -32,6 +32,13 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 F32, BF16 = 0, 1
+
+# phx_residual_ce's contract beyond shift = 0 .. L-1 and all-or-no ds (tests/test_glue_kernel_edges_gpu.py runs the same list in the default
+# mode): (C, H, W, shifts, ds levels handed over) as digit strings -- L = 3 with every way of leaving levels NULL that the all-or-none
+# callers never take, then repeated shifts, no full-resolution level, the 16x level alone, eight levels of eight classes
+RESIDUAL_CE_CONTRACT = [(3, H, W, "012", m) for (H, W) in ((16, 16), (32, 48)) for m in ("100", "010", "001", "101")] + \
+                       [(C, H, W, sh, "1" * len(sh)) for (H, W) in ((16, 16), (32, 48))
+                        for (C, sh) in ((2, "00"), (4, "13"), (3, "024"), (5, "4"), (2, "04"), (8, "00112344"))]
 
 # ---- the table: (name prefix, function, cases).  A function named "K.<name>" lives in tests/test_kernels_gpu.py and is called as
 # f(L, case) (case_star: f(L, *case)); the others are defined below.  Names carry no blanks (the pytest side splits the lines).
@@ -68,6 +75,7 @@ _RERUN = [
     ("wgrad_deferred_multi_layer_reduction", "K.test_wgrad_deferred_multi_layer_reduction", None, [()]),
     ("wgrad_deferred_small_map_launches", "K.test_wgrad_deferred_small_map_launches", None, [()]),
     # both modes (tests/test_kernels_gpu.py runs them too); here a second launch must also give the same bits
+    ("residual_ce_contract", "residual_ce_contract", True, RESIDUAL_CE_CONTRACT),
     ("kl_multi", "kl_multi", True, [(1, True), (3, True), (6, True), (1, False), (3, False), (6, False)]),
 ]
 _MODE_ONLY = [
@@ -308,6 +316,11 @@ def direct_wgrad_single_add(L, B, H, W, Cin, Cout, k, xdt):
 def residual_ce_fixed_point(L, C, H, W, Ls, B):
     from tests import test_kernels_gpu as K
     K._residual_ce_case(L, C, H, W, Ls, B=B, bitwise=True)
+
+
+def residual_ce_contract(L, C, H, W, shifts, ds_levels):
+    from tests import test_kernels_gpu as K
+    K._residual_ce_case(L, C, H, W, len(shifts), bitwise=True, shifts=[int(c) for c in shifts], ds_mask=[c == "1" for c in ds_levels])
 
 
 def kl_multi(L, nlev, grads):
