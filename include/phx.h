@@ -461,6 +461,21 @@ int phx_norm_bwd_apply(const void* dA, int da_dt, const void* x, int x_dt, const
 /* act backward without a norm: dpre = dy * act'(y) evaluated from the stored OUTPUT y */
 int phx_act_bwd(const void* dy, int dy_dt, const void* y, int y_dt, void* dpre, int dpre_dt, size_t n, int act,
                 void* stream);
+/* leaky ReLU as a stream of its own (tfwrapper/activations.py:8-9, tf.maximum(x, alpha * x); csrc/leaky_relu.hip):
+ *   fwd  y    = x >= alpha x ? x : alpha x     one fp32 multiply, then one round-to-nearest-even to y's storage type
+ *   bwd  dpre = y >= 0 ? dy : alpha dy         from the stored OUTPUT y (for 0 < alpha < 1 its sign is x's).  On the tie x == 0 (y = +-0)
+ *                                              the whole gradient passes, as TF's MaximumGrad gives it to the first argument.
+ * x / y (fwd) and dy / y (bwd) are fp32 or bf16 in any combination; dpre takes dy's type (dy_dt != dpre_dt: PHX_E_INVAL).  alpha outside
+ * (0, 1), a NaN included, an unknown dtype code, or a null tensor with n > 0: PHX_E_INVAL, nothing is launched.  n == 0 launches a grid
+ * that touches nothing and returns PHX_OK, as phx_act_bwd does.  y == x and dpre == dy (in place) are allowed and give the bits of the
+ * out-of-place call.  Alignment: a pointer needs the alignment of its element only (2 or 4 bytes; less is PHX_E_INVAL) and n is free.
+ * Pointers off a 16-byte boundary are HANDLED, not refused: where one scalar head of fewer than V elements (V = 4, all tensors fp32, or
+ * 8) brings every tensor to a 16-byte boundary the body moves 16-byte words, otherwise every element moves on its own; the bits are
+ * the same either way and nothing outside [0, n) of any tensor is read or written.  No atomics: the same bits on every run and in
+ * every mode. */
+int phx_leaky_relu_fwd(const void* x, int x_dt, void* y, int y_dt, size_t n, float alpha, void* stream);
+int phx_leaky_relu_bwd(const void* dy, int dy_dt, const void* y, int y_dt, void* dpre, int dpre_dt, size_t n, float alpha,
+                       void* stream);
 
 /* ---- pooling / resize / concat (tfwrapper/layers.py:44-54, 336-345, 70-78; tf.concat) --------------- */
 int phx_avgpool2x2_fwd(const void* x, int dt, void* y, int B, int H, int W, int C, void* stream);

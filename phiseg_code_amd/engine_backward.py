@@ -290,6 +290,16 @@ class BackwardLowering:
             else:
                 self._add_grad(t, write_fn=lambda g: self._emit(self.L.memcpy_d2d, g.ptr, d.ptr, d.nbytes, self.stream))
 
+    def _bw_leaky_relu(self, op):
+        """dx = dy * (y >= 0 ? 1 : alpha) from the node's own output (its input is not read again); an input with further readers gets
+        the contribution through _add_grad, as with dropout and add_act."""
+        d, out = self.grad[op.outputs[0]], self.val[op.outputs[0]]
+
+        def wr(g):
+            dd = self._as_dt(d, g.dt)
+            self._emit(self.L.leaky_relu_bwd, dd.ptr, dd.dt, out.ptr, out.dt, g.ptr, g.dt, out.n, op.attrs["alpha"], self.stream)
+        self._add_grad(op.inputs[0], write_fn=wr)
+
     def _norm_grad_ptrs(self, sv, nv):
         """(gamma, dgamma, dbeta) pointers the norm backward kernels take.  A batch-renorm layer hands them gamma_eff = gamma * r and its
         per-layer scratch: with r and d constant the layer is batch norm with gamma_eff, and the step's tail launch forms the parameter
@@ -393,8 +403,15 @@ class BackwardLowering:
 
     def _bw_global_avgpool(self, op):
         x, d = self.val[op.inputs[0]], self.grad[op.outputs[0]]
-        self._add_grad(op.inputs[0], write_fn=lambda g: self._emit(
-            self.L.global_avgpool_bwd, d.ptr, g.ptr, x.shape[0], x.shape[1] * x.shape[2], x.shape[3], self.stream))
+
+        def wr(g):
+            # the kernel writes fp32: a pooled bf16 tensor (a hidden layer's output; the zoo pools fp32 heads only) takes its gradient
+            # through an fp32 buffer and a cast -- writing fp32 into the bf16 buffer would run past its end
+            t = g if g.dt == F32 else self._alloc(g.shape, F32)
+            self._emit(self.L.global_avgpool_bwd, d.ptr, t.ptr, x.shape[0], x.shape[1] * x.shape[2], x.shape[3], self.stream)
+            if t is not g:
+                self._emit(self.L.cast, t.ptr, F32, g.ptr, g.dt, g.n, self.stream)
+        self._add_grad(op.inputs[0], write_fn=wr)
 
     def _bw_tile_pixels(self, op):
         d = self.grad[op.outputs[0]]

@@ -921,6 +921,16 @@ class ForwardLowering:
         b = self._as_dt(b, a.dt)
         self._emit(self.L.add_act, a.ptr, b.ptr, out.ptr, a.dt, a.n, rt.ACT_CODES[op.attrs["act"]], self.stream)
 
+    def _fw_leaky_relu(self, op, bw):
+        """max(x, alpha x) into a buffer of the node's own: the producer's output stays as it is for its other readers, a fetch and the
+        producer's own backward."""
+        x = self.val[op.inputs[0]]
+        if not isinstance(x, Buf) or x.shift:
+            raise NotImplementedError("leaky_relu %s: its input is not a stored tensor (%s)" % (op.name, type(x).__name__))
+        out = self._alloc(x.shape, x.dt)
+        self.val[op.outputs[0]] = out
+        self._emit(self.L.leaky_relu_fwd, x.ptr, x.dt, out.ptr, out.dt, x.n, op.attrs["alpha"], self.stream)
+
     def _fw_norm_act(self, op, bw):
         """Stand-alone act(normalisation(x)): statistics pass + fused apply (the generic path of the convolution units)."""
         a = op.attrs

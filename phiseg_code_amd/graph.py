@@ -330,6 +330,18 @@ def add_act(a, b, act="identity", name="add"):
     return get_default_graph().add_op("add_act", [a, b], dict(act=act), [(a.shape, a.kind)], name=name)[0]
 
 
+def leaky_relu(x, alpha=0.01, name="leaky_relu"):
+    """tf.maximum(x, alpha * x) (tfwrapper/activations.py:8-9) as a node of its own, on a rank-4 or rank-5 tensor of any layout: same shape
+    and kind as x.  0 < alpha < 1, so that the sign of the output is the sign of the input and the backward pass needs the output only;
+    at x == 0 the whole gradient passes (TF's MaximumGrad on a tie).  DESIGN.md section 7i."""
+    alpha = float(alpha)
+    if not (0.0 < alpha < 1.0 and 0.0 < float(np.float32(alpha)) < 1.0):     # (a NaN fails every comparison; the kernels take an fp32 alpha)
+        raise ValueError("leaky_relu: alpha must lie in (0, 1), got %r" % (alpha,))
+    if not isinstance(x, Tensor) or len(x.shape) not in (4, 5) or x.kind == KIND_U8:
+        raise ValueError("leaky_relu: a rank-4 or rank-5 activation tensor is expected, got %r" % (x,))
+    return get_default_graph().add_op("leaky_relu", [x], dict(alpha=alpha), [(x.shape, x.kind)], name=name)[0]
+
+
 def norm_act(x, norm, norm_vars, act, training, num_groups=None, name="norm"):
     """act(normalisation(x)) as a node of its own: the pre-activation order of identity_residual_unit2D (layers.py:512-518), where
     the normalisation does not follow a convolution."""

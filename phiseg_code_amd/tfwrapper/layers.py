@@ -7,7 +7,10 @@ runs in hand-written HIP kernels (libphx.so).  The layers that no PHiSeg configu
 kernels: strided / dilated / transposed convolutions, residual units, dense, max pool, pad and crop (csrc/gconv.hip, csrc/tconv.hip),
 and the 3-D family -- ``conv3D``, ``transposed_conv3D``, ``maxpool3D``, ``bilinear_upsample3D`` and the 5-D branch of
 ``crop_and_concat`` on NDHWC tensors [B, D, H, W, C] (csrc/conv3d.hip).  3-D units take tfnorm.identity or
-tfnorm.batch_norm; what a layer does not support raises NotImplementedError with the reason.
+tfnorm.batch_norm; what a layer does not support raises NotImplementedError with the reason.  Every ``activation=`` also takes
+``activations.leaky_relu`` (or a ``functools.partial`` of it with ``alpha``): the unit then carries the identity and a
+``graph.leaky_relu`` node follows it; ``normalise_post_activation=True`` is the unit without normalisation followed by a
+normalisation node (``_unit``).
 """
 import logging
 
@@ -33,6 +36,43 @@ def global_averagepool2D(x, name=None):
     return G.global_average_pool(x, name=name)
 
 
+def global_averagepool3D(x, name=None):
+    """tf.reduce_mean(x, axis=(1, 2, 3)) (tfwrapper/layers.py:81-91): [B, D, H, W, C] -> [B, C], as the 2-D pool of the same memory seen
+    as [B, D * H, W, C] (fold_depth: a view, no launch)."""
+    if len(x.get_shape().as_list()) != 5:
+        raise ValueError("global_averagepool3D: a [B, D, H, W, C] tensor is expected, got %r" % (x,))
+    return G.global_average_pool(G.fold_depth(x), name=name)
+
+
+def _check_callables(normalisation, activation):
+    if normalisation not in tfnorm.KIND:
+        raise ValueError("Unknown normalisation callable %r" % (normalisation,))
+    if not activations.known(activation):
+        raise ValueError("Unknown activation callable %r" % (activation,))
+    alpha = activations.leaky_alpha(activation)
+    if alpha is not None and not 0.0 < alpha < 1.0:      # (before any variable is made; graph.leaky_relu has the last word)
+        raise ValueError("leaky_relu: alpha must lie in (0, 1), got %r" % (alpha,))
+
+
+def _leaky(op, alpha):
+    """the leaky_relu node behind a unit that carries the identity (alpha None: any other activation, which the unit applied itself)"""
+    return op if alpha is None else G.leaky_relu(op, alpha)
+
+
+def _unit(x, weights, biases, ksize, kind, norm_vars, activation, training, num_groups, head, name, post=False, **geometry):
+    """conv -> [bias] -> normalisation -> activation as ONE conv_unit node; or -- `post` (normalise_post_activation) with a normalisation
+    to apply -- conv -> [bias] -> activation as the unit and a normalisation node behind it under the same scope (the way _volume_unit
+    has always built it).  leaky_relu is a node of its own behind a unit that carries the identity; such a unit is a hidden layer, never
+    a head, so it keeps the plan's activation storage."""
+    an, alpha = activations.unit_act(activation)
+    if post and kind is not None:
+        op = G.conv_unit(x, weights, biases, ksize, None, {}, an, training, head=False, name=name, **geometry)
+        return G.norm_act(_leaky(op, alpha), kind, norm_vars, 'identity', training, num_groups=num_groups, name='norm')
+    op = G.conv_unit(x, weights, biases, ksize, kind, norm_vars, an, training, num_groups=num_groups, head=head and alpha is None,
+                     name=name, **geometry)
+    return _leaky(op, alpha)
+
+
 def conv2D(x,
            name,
            kernel_size=(3, 3),
@@ -46,21 +86,16 @@ def conv2D(x,
            weight_init='he_normal',
            add_bias=True,
            **kwargs):
-    """Standard 2-D convolutional layer: conv -> [bias] -> normalisation -> activation.
-    kwargs can carry ``training`` and normalisation parameters (``num_groups``)."""
+    """Standard 2-D convolutional layer: conv -> [bias] -> normalisation -> activation (normalise_post_activation: activation ->
+    normalisation) [-> dropout].  kwargs can carry ``training`` and normalisation parameters (``num_groups``)."""
     if padding != "SAME":
         raise NotImplementedError("conv2D: SAME padding (the only value the reference's call sites use)")
-    if normalise_post_activation:
-        raise NotImplementedError("normalise_post_activation is never set by the PHiSeg configs")
     # stride 1 with a 1x1 / 3x3 kernel is the hot path (MFMA / direct / head kernels); anything else -- strided convolutions of the
     # residual units, larger kernels -- runs on the general direct kernels of csrc/gconv.hip
     general = None
     if tuple(strides) != (1, 1) or tuple(kernel_size) not in ((1, 1), (3, 3)):
         general = (int(kernel_size[0]), int(kernel_size[1]), int(strides[0]), int(strides[1]), 1, 1)
-    if normalisation not in tfnorm.KIND:
-        raise ValueError("Unknown normalisation callable %r" % (normalisation,))
-    if activation not in activations.ACT_NAME:
-        raise ValueError("Unknown activation callable %r" % (activation,))
+    _check_callables(normalisation, activation)
 
     bottom_num_filters = x.get_shape().as_list()[-1]
     weight_shape = [kernel_size[0], kernel_size[1], bottom_num_filters, num_filters]
@@ -71,6 +106,7 @@ def conv2D(x,
         weights = utils.get_weight_variable(weight_shape, name='W', type=weight_init, regularize=True)
         biases = None
         if add_bias and normalisation in (tfnorm.batch_norm, tfnorm.batch_renorm):
+            # (decided before the order of normalisation and activation is looked at, as in the reference: layers.py:126-128.)
             # (batch_renorm: the reference keeps the bias there; with r and d constant for the gradient it gets none and stays at its
             # zero initial value, so leaving it out changes no result -- DESIGN.md section 7f)
             logging.debug('Turning of bias because using batch norm.')
@@ -82,8 +118,8 @@ def conv2D(x,
         training = kwargs.get('training', True)
         # heads (mu / sigma / logits) keep fp32 storage in the bf16 configuration
         head = kind is None and activation is not activations.relu and general is None
-        op = G.conv_unit(x, weights, biases, kernel_size[0], kind, norm_vars, activations.ACT_NAME[activation],
-                         training, num_groups=kwargs.get('num_groups'), head=head, name='conv', general=general)
+        op = _unit(x, weights, biases, kernel_size[0], kind, norm_vars, activation, training, kwargs.get('num_groups'), head, 'conv',
+                   post=normalise_post_activation, general=general)
         if dropout_p is not None:
             op = dropout(op, keep_prob=dropout_p, training=training)
         return op
@@ -103,11 +139,11 @@ def dilated_conv2D(bottom,
                    add_bias=True,
                    **kwargs):
     """tfwrapper/layers.py:378-425: tf.nn.atrous_conv2d(bottom, W, rate, SAME) -> [bias] -> normalisation -> activation
-    [-> dropout].  (Unlike conv2D the bias is kept in front of batch_norm, layers.py:406-409.)"""
-    if padding != "SAME" or normalise_post_activation:
-        raise NotImplementedError("dilated_conv2D: SAME padding, normalisation before the activation")
-    if normalisation not in tfnorm.KIND or activation not in activations.ACT_NAME:
-        raise ValueError("Unknown normalisation / activation callable")
+    (normalise_post_activation: activation -> normalisation) [-> dropout].  (Unlike conv2D the bias is kept in front of batch_norm,
+    layers.py:406-409.)"""
+    if padding != "SAME":
+        raise NotImplementedError("dilated_conv2D: SAME padding")
+    _check_callables(normalisation, activation)
     cin = bottom.get_shape().as_list()[3]
     g = G.get_default_graph()
     with g.variable_scope(name):
@@ -117,9 +153,9 @@ def dilated_conv2D(bottom,
         kind = tfnorm.KIND[normalisation]
         norm_vars = tfnorm.make_variables(kind, num_filters)
         training = kwargs.get('training', True)
-        op = G.conv_unit(bottom, weights, biases, kernel_size[0], kind, norm_vars, activations.ACT_NAME[activation], training,
-                         num_groups=kwargs.get('num_groups'), head=False, name='atrous',
-                         general=(int(kernel_size[0]), int(kernel_size[1]), 1, 1, int(rate), int(rate)))
+        op = _unit(bottom, weights, biases, kernel_size[0], kind, norm_vars, activation, training, kwargs.get('num_groups'), False,
+                   'atrous', post=normalise_post_activation,
+                   general=(int(kernel_size[0]), int(kernel_size[1]), 1, 1, int(rate), int(rate)))
         if dropout_p is not None:
             op = dropout(op, keep_prob=dropout_p, training=training)
         return op
@@ -136,12 +172,9 @@ def dense_layer(bottom,
                 add_bias=True,
                 **kwargs):
     """tfwrapper/layers.py:539-582: flatten -> matmul with W [F, hidden_units] -> [bias] -> normalisation -> activation
-    [-> dropout].  Runs as a 1x1 convolution of the flattened input; the result keeps two unit axes: [B, 1, 1, hidden_units]
-    (same memory as the reference's [B, hidden_units])."""
-    if normalise_post_activation:
-        raise NotImplementedError("dense_layer: normalisation before the activation only")
-    if normalisation not in tfnorm.KIND or activation not in activations.ACT_NAME:
-        raise ValueError("Unknown normalisation / activation callable")
+    (normalise_post_activation: activation -> normalisation) [-> dropout].  Runs as a 1x1 convolution of the flattened input; the
+    result keeps two unit axes: [B, 1, 1, hidden_units] (same memory as the reference's [B, hidden_units])."""
+    _check_callables(normalisation, activation)
     flat = G.flatten(bottom)
     f = flat.get_shape().as_list()[3]
     g = G.get_default_graph()
@@ -151,8 +184,8 @@ def dense_layer(bottom,
         kind = tfnorm.KIND[normalisation]
         norm_vars = tfnorm.make_variables(kind, hidden_units)
         training = kwargs.get('training', True)
-        op = G.conv_unit(flat, weights, biases, 1, kind, norm_vars, activations.ACT_NAME[activation], training,
-                         num_groups=kwargs.get('num_groups'), head=False, name='dense', general=(1, 1, 1, 1, 1, 1))
+        op = _unit(flat, weights, biases, 1, kind, norm_vars, activation, training, kwargs.get('num_groups'), False, 'dense',
+                   post=normalise_post_activation, general=(1, 1, 1, 1, 1, 1))
         if dropout_p is not None:
             op = dropout(op, keep_prob=dropout_p, training=training)
         return op
@@ -173,8 +206,8 @@ def _conv_norm(x, conv_name, norm_scope, num_filters, strides, kernel_size, norm
     general = None
     if tuple(strides) != (1, 1) or tuple(kernel_size) not in ((1, 1), (3, 3)):
         general = (int(kernel_size[0]), int(kernel_size[1]), int(strides[0]), int(strides[1]), 1, 1)
-    return G.conv_unit(x, weights, biases, kernel_size[0], kind, norm_vars, activations.ACT_NAME[activation],
-                       kwargs.get('training', True), num_groups=kwargs.get('num_groups'), head=False, name=conv_name, general=general)
+    return _unit(x, weights, biases, kernel_size[0], kind, norm_vars, activation, kwargs.get('training', True), kwargs.get('num_groups'),
+                 False, conv_name, general=general)
 
 
 def _residual_skip(x, num_filters, down_sample, projection, strides, activation, normalisation, add_bias, kwargs):
@@ -201,8 +234,8 @@ def residual_unit2D(x,
                     add_bias=True,
                     **kwargs):
     """tfwrapper/layers.py:428-478 (https://arxiv.org/abs/1512.03385): conv1 -> bn1 -> act -> conv2 -> bn2, + skip, -> act."""
-    if normalisation not in tfnorm.KIND or activation not in activations.ACT_NAME:
-        raise ValueError("Unknown normalisation / activation callable")
+    _check_callables(normalisation, activation)
+    an, alpha = activations.unit_act(activation)
     strides = (2, 2) if down_sample else (1, 1)
     g = G.get_default_graph()
     with g.variable_scope(name):
@@ -212,7 +245,7 @@ def residual_unit2D(x,
         if skip.get_shape().as_list()[-1] != num_filters:
             raise ValueError("residual_unit2D: channel padding needs an even difference (%d -> %d)"
                              % (x.get_shape().as_list()[-1], num_filters))
-        return G.add_act(skip, conv2, activations.ACT_NAME[activation], name='add')
+        return _leaky(G.add_act(skip, conv2, an, name='add'), alpha)
 
 
 def identity_residual_unit2D(x,
@@ -225,8 +258,7 @@ def identity_residual_unit2D(x,
                              add_bias=True,
                              **kwargs):
     """tfwrapper/layers.py:481-536 (identity mappings, pre-activation order): bn1 -> act -> conv1 -> bn2 -> act -> conv2, + skip."""
-    if normalisation not in tfnorm.KIND or activation not in activations.ACT_NAME:
-        raise ValueError("Unknown normalisation / activation callable")
+    _check_callables(normalisation, activation)
     cin = x.get_shape().as_list()[-1]
     if not projection:
         assert (cin == num_filters) or (cin * 2 == num_filters), \
@@ -235,7 +267,7 @@ def identity_residual_unit2D(x,
     strides = (2, 2) if down_sample else (1, 1)
     training = kwargs.get('training', True)
     kind = tfnorm.KIND[normalisation]
-    an = activations.ACT_NAME[activation]
+    an, alpha = activations.unit_act(activation)
     g = G.get_default_graph()
 
     def conv(t, cname, st):
@@ -247,10 +279,10 @@ def identity_residual_unit2D(x,
         return G.conv_unit(t, weights, biases, 3, None, {}, 'identity', training, head=False, name=cname, general=general)
     with g.variable_scope(name):
         op1 = G.norm_act(x, kind, tfnorm.make_variables(kind, cin, scope='bn1'), an, training, kwargs.get('num_groups'), name='bn1')
-        op1 = conv(op1, 'conv1', strides)
+        op1 = conv(_leaky(op1, alpha), 'conv1', strides)
         op2 = G.norm_act(op1, kind, tfnorm.make_variables(kind, num_filters, scope='bn2'), an, training, kwargs.get('num_groups'),
                          name='bn2')
-        op2 = conv(op2, 'conv2', (1, 1))
+        op2 = conv(_leaky(op2, alpha), 'conv2', (1, 1))
         skip = _residual_skip(x, num_filters, down_sample, projection, strides, activation, normalisation, add_bias, kwargs)
         return G.add_act(skip, op2, 'identity', name='add')
 
@@ -309,16 +341,12 @@ def transposed_conv2D(bottom,
                       add_bias=True,
                       **kwargs):
     """Standard 2-D transposed convolution (tfwrapper/layers.py:197-258): tf.nn.conv2d_transpose with a [kh, kw, num_filters,
-    bottom channels] filter, default behaviour up-samples by a factor of 2; -> [bias] -> normalisation -> activation.  Unlike
-    conv2D the reference keeps the bias here even in front of batch_norm (layers.py:231-234)."""
+    bottom channels] filter, default behaviour up-samples by a factor of 2; -> [bias] -> normalisation -> activation
+    (normalise_post_activation: activation -> normalisation) [-> dropout].  Unlike conv2D the reference keeps the bias here even in
+    front of batch_norm (layers.py:231-234)."""
     if padding != "SAME":
         raise NotImplementedError("transposed_conv2D: SAME padding (the reference's default) only")
-    if normalise_post_activation or dropout_p is not None:
-        raise NotImplementedError("normalise_post_activation / dropout are never set by the PHiSeg configs")
-    if normalisation not in tfnorm.KIND:
-        raise ValueError("Unknown normalisation callable %r" % (normalisation,))
-    if activation not in activations.ACT_NAME:
-        raise ValueError("Unknown activation callable %r" % (activation,))
+    _check_callables(normalisation, activation)
     shp = bottom.get_shape().as_list()
     if output_shape is not None and tuple(output_shape[1:3]) != (shp[1] * strides[0], shp[2] * strides[1]):
         raise NotImplementedError("transposed_conv2D: output_shape other than input * strides")
@@ -329,9 +357,13 @@ def transposed_conv2D(bottom,
         biases = utils.get_bias_variable([num_filters], name='b') if add_bias else None
         kind = tfnorm.KIND[normalisation]
         norm_vars = tfnorm.make_variables(kind, num_filters)
-        return G.conv_unit(bottom, weights, biases, kernel_size[0], kind, norm_vars, activations.ACT_NAME[activation],
-                           kwargs.get('training', True), num_groups=kwargs.get('num_groups'), head=False, name='deconv',
-                           transposed=(int(kernel_size[0]), int(kernel_size[1]), int(strides[0]), int(strides[1])))
+        training = kwargs.get('training', True)
+        op = _unit(bottom, weights, biases, kernel_size[0], kind, norm_vars, activation, training, kwargs.get('num_groups'), False,
+                   'deconv', post=normalise_post_activation,
+                   transposed=(int(kernel_size[0]), int(kernel_size[1]), int(strides[0]), int(strides[1])))
+        if dropout_p is not None:
+            op = dropout(op, keep_prob=dropout_p, training=training)
+        return op
 
 
 def nearest_neighbour_upsample2D(x, factor):
@@ -397,10 +429,7 @@ def _volume_unit(x, name, form, kernel_size, num_filters, strides, activation, n
     """What conv3D and transposed_conv3D share: W (and b, kept even in front of batch norm: layers.py:178-181, 307-310) under `name`,
     conv -> bias -> normalisation -> activation as one unit, or -- normalise_post_activation -- the unit with the activation and no
     normalisation followed by a normalisation node under the same scope, then dropout."""
-    if normalisation not in tfnorm.KIND:
-        raise ValueError("Unknown normalisation callable %r" % (normalisation,))
-    if activation not in activations.ACT_NAME:
-        raise ValueError("Unknown activation callable %r" % (activation,))
+    _check_callables(normalisation, activation)
     kind = tfnorm.KIND[normalisation]
     if kind not in (None, "batch"):
         why = {"group": "group_norm2D reshapes a rank-4 tensor and fails on a volume in the reference itself",
@@ -416,7 +445,6 @@ def _volume_unit(x, name, form, kernel_size, num_filters, strides, activation, n
     weight_shape = [kd, kh, kw, cin, num_filters] if form == "conv" else [kd, kh, kw, num_filters, cin]
     g = G.get_default_graph()
     training = kwargs.get('training', True)
-    an = activations.ACT_NAME[activation]
     volume = (form, kd, kh, kw) + tuple(int(s) for s in strides)
     with g.variable_scope(name):
         weights = utils.get_weight_variable(weight_shape, name='W', type=weight_init, regularize=True)
@@ -425,11 +453,8 @@ def _volume_unit(x, name, form, kernel_size, num_filters, strides, activation, n
         # heads (identity normalisation, activation other than relu) keep fp32 storage in the bf16 configuration, as in conv2D
         head = kind is None and activation is not activations.relu
         uname = 'conv' if form == "conv" else 'deconv'
-        if normalise_post_activation and kind is not None:
-            op = G.conv_unit(x, weights, biases, kd, None, {}, an, training, head=False, name=uname, volume=volume)
-            op = G.norm_act(op, kind, norm_vars, 'identity', training, name='norm')
-        else:
-            op = G.conv_unit(x, weights, biases, kd, kind, norm_vars, an, training, head=head, name=uname, volume=volume)
+        op = _unit(x, weights, biases, kd, kind, norm_vars, activation, training, None, head, uname, post=normalise_post_activation,
+                   volume=volume)
         if dropout_p is not None:
             op = dropout(op, keep_prob=dropout_p, training=training)
         return op
