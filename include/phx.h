@@ -717,6 +717,41 @@ int phx_mc_stats(const float* logits, const float* sm, const unsigned char* gt, 
 /* eval_xent (phiseg_model.py:111) of one graph instance: out[p] = logsumexp(logits[p][:]) - logits[p][labels[p]], npix pixels */
 int phx_softmax_xent_map(const float* logits, const unsigned char* labels, float* out, size_t npix, int C, void* stream);
 
+/* ---- many classes: 9 <= C <= 256 (csrc/many_class.hip) -------------------------------------------------------------------------
+ * The entries above that meet class counts -- phx_residual_ce, phx_softmax_xent_map, phx_validation_metrics, phx_eval_metrics -- keep
+ * one pixel's classes in registers and refuse C > 8; they stay as they are.  The entries below take 9 <= C <= 256 only (anything else:
+ * PHX_E_SHAPE, nothing is launched; 256 is the range of the u8 label maps) and walk the classes in chunks of 8, so what a thread keeps
+ * does not grow with C.  The host chooses by C (phiseg_code_amd/many_class.py).  A pixel's chunk is read and written as two 16-byte
+ * words where it is whole and its address 16-byte aligned, element by element otherwise (any C, any 4-byte aligned base).  No
+ * floating-point atomics: partial sums are stored per block and added in a fixed order, so two calls on the same input give the same
+ * bits whether or not PHX_DETERMINISTIC is set.
+ *
+ * phx_residual_ce_wide: the arguments and contract of phx_residual_ce (nullable ds[l], each written with plain stores, one writer per
+ *   element; labels NULL with s_out / sm_out on the sampling path; shift[l] <= 4, L <= 8), except that `losses` holds 8 floats only and
+ *   the loss partials go to `work`: phx_residual_ce_wide_ws_bytes(B, H, W) bytes, 4-byte aligned, needed when losses is set
+ *   (PHX_E_INVAL otherwise, and for losses without labels); work may be NULL when losses is.
+ * phx_softmax_xent_map_wide: phx_softmax_xent_map, the log-sum-exp taken online over the class chunks.
+ * phx_metrics_wide: GED over labels label0 .. C-1, variance-NCC and per-label Dice with the definitions of phx_eval_metrics, one entry
+ *   for both label layouts:
+ *     sm          [I * N][P][C] f32 soft-max, rows i * N + k (the layout of both narrow entries)
+ *     labels      u8, image stride M * P; annotator j of pixel p at j * lab_annot_stride + p * lab_pixel_stride: strides (P, 1) read
+ *                 [I][M][P] (phx_validation_metrics), strides (1, M) read [I][P][M] (phx_eval_metrics); anything else PHX_E_INVAL
+ *     sref_map    [I][P] u8 the map the Dice is taken against, or NULL;  sref_annot [I] u8 DEVICE array, the annotator whose map it is
+ *                 taken against (an index >= M reads annotator M - 1), or NULL.  Both set: PHX_E_INVAL; both NULL: no Dice
+ *     out         [I][2 + C] f32: GED, NCC, Dice per label (all Dice slots 0 without a reference)
+ *     work        phx_metrics_wide_ws_bytes bytes, 8-byte aligned (too small: PHX_E_INVAL)
+ *   Label maps are kept as byte maps; a (mask, mask) pair is one wave that counts labels in its own LDS histogram (integer adds).  Sums
+ *   over samples and pixels are double. */
+size_t phx_residual_ce_wide_ws_bytes(int B, int H, int W);
+int phx_residual_ce_wide(const float* const* s, float* const* ds, const int* shift, int L, const uint8_t* labels, int B, int H, int W,
+                         int C, float weight, float inv_batch, float* losses, float* s_out, float* sm_out, void* work,
+                         size_t work_bytes, void* stream);
+int phx_softmax_xent_map_wide(const float* logits, const unsigned char* labels, float* out, size_t npix, int C, void* stream);
+size_t phx_metrics_wide_ws_bytes(int I, int N, int M, int P, int C);
+int phx_metrics_wide(const float* sm, const unsigned char* labels, size_t lab_annot_stride, size_t lab_pixel_stride,
+                     const unsigned char* sref_map, const unsigned char* sref_annot, void* work, size_t work_bytes, int I, int N, int M,
+                     int P, int C, int label0, float* out, void* stream);
+
 /* ---- TensorBoard summaries on the device (phiseg_model.py:199-203, 704-818; tfwrapper/layers.py:671-677; csrc/summary.hip) -------
  * phx_summary_histograms: what tf.summary.histogram computes on the host, for a LIST of segments in one launch (+ a memset and an
  * nseg-thread finishing launch).  TensorFlow 1.12's default buckets (core/lib/histogram/histogram.cc): the caller builds the 1551
@@ -818,6 +853,25 @@ size_t phx_augment_batch_elastic_ws_bytes(int B, int X, int Y);
 int phx_augment_batch_elastic(const float* images, const unsigned char* labels, const void* params_dev, const double* ctrl_dev,
                               float* x_out, unsigned char* s_out, void* workspace, size_t workspace_bytes, int B, int X, int Y, int A,
                               int nlabels, void* stream);
+
+/* The reference's `nlabels > 4` branch (data/batch_provider.py:204-208, 221-224, 245-248; csrc/augment_nearest.hip): the image takes the
+ * linear path of the two entries above, unchanged; the label map is resampled with cv2.INTER_NEAREST -- one source pixel per stage, in
+ * the reference's stage order rotate, crop-scale, elastic, flips, so the stages compose into a chain of coordinates.  The rules are
+ * restated from OpenCV's published algorithms -- BELIEVED, NOT EXECUTABLE HERE (OpenCV is not installed; the same standing as the linear
+ * path, see oracle/augment.py); tests/augment_nearest_ref.py restates them in numpy:
+ *   cv2.warpAffine(..., INTER_NEAREST)        the fixed-point grid of the linear path with round_delta = AB_SCALE / 2: source pixel
+ *                                             (X0 + adelta[x]) >> AB_BITS, BORDER_CONSTANT 0 outside
+ *   cv2.resize(crop, INTER_NEAREST)           sx = min(floor(dx * (src / dst)), src - 1) per axis, in double; no half-pixel centre
+ *   cv2.remap(INTER_NEAREST, BORDER_REFLECT)  on the float32 maps of deformation_to_transformation (no convertMaps): cvRound (half to
+ *                                             even) of each map value, reflect-including-edge border
+ * Arguments as phx_augment_batch_elastic.  ctrl_dev NULL: the plain producer (a record's elastic bit is not read).  5 <= nlabels <= 256
+ * (anything else PHX_E_SHAPE: the two entries above keep nlabels <= 4).  workspace: phx_augment_batch_nearest_ws_bytes(B, X, Y,
+ * elastic = ctrl_dev != NULL) bytes, 4-byte aligned (0 where the intermediates fit LDS). */
+size_t phx_augment_batch_nearest_ws_bytes(int B, int X, int Y, int elastic);
+int phx_augment_batch_nearest(const float* images, const unsigned char* labels, const void* params_dev, const double* ctrl_dev,
+                              float* x_out, unsigned char* s_out, void* workspace, size_t workspace_bytes, int B, int X, int Y, int A,
+                              int nlabels, void* stream);
+
 
 /* ---- layer normalisation (tfwrapper/normalisation.py:39-68 through layers.conv2D: no gamma / beta, axes (1, 2, 3); csrc/layer_norm.hip) ----
  * Per sample b over all N = H W C contiguous values of y [B][N]:

@@ -3,7 +3,8 @@ _select_random_label, _augmentation_function) and data/lidc_data.py (the .train 
 
 The data set is uploaded to HBM once (LIDC train split: ~1 GB of images + ~1 GB of 4-annotator masks -- a fraction of a
 per cent of 288 GB); a batch is then ONE kernel (phx_augment_batch: gather, random annotator, rotation, crop-scale, flips;
-phx_augment_batch_elastic when 'do_elasticaug' is set: the same plus the random elastic deformation of batch_provider.py:226-248)
+phx_augment_batch_elastic when 'do_elasticaug' is set: the same plus the random elastic deformation of batch_provider.py:226-248;
+phx_augment_batch_nearest, plain or elastic, when there are more than four labels: the reference's cv2.INTER_NEAREST branch)
 whose outputs can be the training plan's own input buffers -- no host round trip, where the reference spends the training
 thread on numpy / OpenCV per step (phiseg_model.py:193).
 
@@ -17,6 +18,7 @@ import math
 
 import numpy as np
 
+from phiseg_code_amd import many_class
 from phiseg_code_amd import philox_host
 
 ROTATE, SCALE, FLIPLR, FLIPUD, ELASTIC = 1, 2, 4, 8, 16
@@ -162,7 +164,16 @@ class DeviceBatchProvider:
         else:
             xo = so = None
         st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        if ctrl is None:
+        if many_class.label_route(self.nlabels) == "nearest":        # more than four labels: nearest-neighbour label maps, plain or elastic
+            key = ("nearest", batch_size)
+            if key not in self._ws:
+                nb = self.L.augment_batch_nearest_ws_bytes(batch_size, Xs, Ys, 1 if ctrl is not None else 0)
+                self._ws[key] = (torch.empty(nb, dtype=torch.uint8, device=par.device) if nb else None, nb)
+            ws, nb = self._ws[key]
+            self.L.augment_batch_nearest(self.images_dev.data_ptr(), self.labels_dev.data_ptr(), par.data_ptr(),
+                                         par.data_ptr() + rec.nbytes if ctrl is not None else None, x_ptr, s_ptr,
+                                         ws.data_ptr() if nb else None, nb, batch_size, Xs, Ys, self.n_annot, self.nlabels, st)
+        elif ctrl is None:
             self.L.augment_batch(self.images_dev.data_ptr(), self.labels_dev.data_ptr(), par.data_ptr(), x_ptr, s_ptr, batch_size,
                                  Xs, Ys, self.n_annot, self.nlabels, st)
         else:

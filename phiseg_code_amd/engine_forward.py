@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from phiseg_code_amd import graph as G
+from phiseg_code_amd import many_class
 from phiseg_code_amd import runtime as rt
 from phiseg_code_amd import upconv
 from phiseg_code_amd.tfwrapper import normalisation as tfnorm
@@ -1117,8 +1118,14 @@ class ForwardLowering:
                     dbufs.append(self._alloc(b.shape, F32))
             dsp = rt.ptr_array([b.ptr for b in dbufs])
             self.saved[op] = dict(dbufs=dbufs, src=[t.op.inputs[0] if t.op.type == "nn_resize" else t for t in s_t])
-        self._emit(self.L.residual_ce, sp, dsp, shp, Ls, lab.ptr, B, H, W, C, w, self.inv_batch, losses.ptr,
-                   s_out.ptr, None, self.stream)
+        if many_class.residual_ce_entry(C) == "residual_ce":
+            self._emit(self.L.residual_ce, sp, dsp, shp, Ls, lab.ptr, B, H, W, C, w, self.inv_batch, losses.ptr,
+                       s_out.ptr, None, self.stream)
+        else:
+            wsb = int(self.L.residual_ce_wide_ws_bytes(B, H, W))
+            work = self._alloc((wsb // 4,), F32)
+            self._emit(self.L.residual_ce_wide, sp, dsp, shp, Ls, lab.ptr, B, H, W, C, w, self.inv_batch, losses.ptr,
+                       s_out.ptr, None, work.ptr, wsb, self.stream)
 
     def _fw_aggregate(self, op, bw):
         Ls = op.attrs["L"]
@@ -1126,15 +1133,19 @@ class ForwardLowering:
         s_out, sm = self._alloc_like(op.outputs[0]), self._alloc_like(op.outputs[1])
         self.val[op.outputs[0]], self.val[op.outputs[1]] = s_out, sm
         B, H, W, C = s_out.shape
-        self._emit(self.L.residual_ce, sp, None, shp, Ls, None, B, H, W, C, 0.0, 1.0, None, s_out.ptr, sm.ptr,
-                   self.stream)
+        if many_class.residual_ce_entry(C) == "residual_ce":
+            self._emit(self.L.residual_ce, sp, None, shp, Ls, None, B, H, W, C, 0.0, 1.0, None, s_out.ptr, sm.ptr,
+                       self.stream)
+        else:
+            self._emit(self.L.residual_ce_wide, sp, None, shp, Ls, None, B, H, W, C, 0.0, 1.0, None, s_out.ptr, sm.ptr,
+                       None, 0, self.stream)
 
     def _fw_xent_map(self, op, bw):
         lg, lab = self.val[op.inputs[0]], self.val[op.inputs[1]]
         assert lg.dt == F32 and lg.shift == 0, "eval_xent reads the summed full-resolution logits"
         out = self._alloc_like(op.outputs[0])
         self.val[op.outputs[0]] = out
-        self._emit(self.L.softmax_xent_map, lg.ptr, lab.ptr, out.ptr, out.n, lg.shape[-1], self.stream)
+        self._emit(getattr(self.L, many_class.xent_map_entry(lg.shape[-1])), lg.ptr, lab.ptr, out.ptr, out.n, lg.shape[-1], self.stream)
 
     # ---- tfwrapper/losses.py (csrc/seg_losses.hip) ------------------------------------------------------------------------------
     def _seg_loss_args(self, op):

@@ -5,7 +5,7 @@ The reference scores a test set with phiseg_test_quantitative.py (GED / NCC over
 mean of 100 samples): per image one sess.run, the samples pulled to the host, the IoU loops in Python.  Here a pass feeds
 `images_per_pass` images, draws all their samples at once (model.sampling_graph where the prior shares an x-only encoder, x repeated
 on s_out_eval_sm otherwise -- the policy of phiseg._mc_maps), and the scoring kernel reads the plan's soft-max buffer in place on the
-plan's stream; a pass ends with one wait for its stream (the noise step must not move under it), and only the [n, 10] score table
+plan's stream; a pass ends with one wait for its stream (the noise step must not move under it), and only the [n, 2 + max(C, 8)] score table
 comes back, once, at the end.  phiseg_test_quantitative / phiseg_test_predictions of this package are the reference's two scripts over
 evaluate_split."""
 import glob
@@ -26,6 +26,7 @@ def evaluate_split(model, split, num_samples, images_per_pass=DEFAULT_IMAGES_PER
     image order before the first pass, as _do_validation draws it (annotator_range: default exp_config.annotator_range).
     The noise step advances once per pass.  -> dict(ged [n], ncc [n], dice [n, nlabels], sref_annot [n])."""
     import torch
+    from phiseg_code_amd import many_class
     from phiseg_code_amd import runtime as rt
     L = rt.lib()
     cfg = model.exp_config
@@ -52,8 +53,10 @@ def evaluate_split(model, split, num_samples, images_per_pass=DEFAULT_IMAGES_PER
     if labels_dev.dtype != torch.uint8 or tuple(labels_dev.shape) != tuple(labels.shape) or not labels_dev.is_contiguous():
         raise ValueError("labels_dev must be a contiguous uint8 tensor of shape %s" % (tuple(labels.shape),))
     sref_dev = torch.as_tensor(sref.astype(np.uint8)).to(dev)
-    out = torch.empty(total, 10, dtype=torch.float32, device=dev)
-    wsb = int(L.eval_metrics_ws_bytes(min(ipp, total), n, A, P, C))
+    wide = many_class.eval_metrics_entry(C) == "metrics_wide"
+    row = many_class.metrics_row(C)
+    out = torch.empty(total, row, dtype=torch.float32, device=dev)
+    wsb = int((L.metrics_wide_ws_bytes if wide else L.eval_metrics_ws_bytes)(min(ipp, total), n, A, P, C))
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)       # one scratch for every pass
     one_pass = n > 1 and model._one_pass_prior()
     sm_t = model.sampling_graph(n)[1] if one_pass else model.s_out_eval_sm
@@ -68,8 +71,12 @@ def evaluate_split(model, split, num_samples, images_per_pass=DEFAULT_IMAGES_PER
         if sm.dt != rt.F32 or sm.shift or tuple(sm.shape) != (b * n, X, Y, C):
             raise rt.PhxError("evaluate_split: the soft-max buffer is %s (dtype code %d), expected float32 %s"
                               % (sm.shape, sm.dt, (b * n, X, Y, C)))
-        L.eval_metrics(sm.ptr, labels_dev.data_ptr() + i0 * P * A, sref_dev.data_ptr() + i0, ws.data_ptr(), wsb, b, n, A, P, C, 1,
-                       out.data_ptr() + i0 * 10 * 4, plan.stream)
+        if wide:
+            L.metrics_wide(sm.ptr, labels_dev.data_ptr() + i0 * P * A, 1, A, None, sref_dev.data_ptr() + i0, ws.data_ptr(), wsb, b, n, A, P,
+                           C, 1, out.data_ptr() + i0 * row * 4, plan.stream)
+        else:
+            L.eval_metrics(sm.ptr, labels_dev.data_ptr() + i0 * P * A, sref_dev.data_ptr() + i0, ws.data_ptr(), wsb, b, n, A, P, C, 1,
+                           out.data_ptr() + i0 * row * 4, plan.stream)
         # The pass reads the Philox step word on the device: it must have finished before the word moves (as in phiseg._mc_maps).
         # This wait is the only one of a pass and nothing is copied: the scores stay in `out` until every pass has run.
         plan.sync()

@@ -22,6 +22,7 @@ import numpy as np
 
 from phiseg_code_amd import engine
 from phiseg_code_amd import graph as G
+from phiseg_code_amd import many_class
 from phiseg_code_amd import optimizers
 from phiseg_code_amd import utils
 from phiseg_code_amd.tfwrapper import normalisation as tfnorm
@@ -260,7 +261,8 @@ class phiseg():
         self.dist = dist
 
     def checks(self):
-        pass
+        # the label maps are uint8 and the class-aware kernels stop at 256 classes: say so here, not from inside the first launch
+        many_class.check_nlabels(self.exp_config.nlabels)
 
     def add_loss_term(self, name, scalar, weight=1.0):
         """Add a scalar of the caller's making (tfwrapper.losses.dice_loss, cross_entropy_loss, ... on a tensor of this model) to the

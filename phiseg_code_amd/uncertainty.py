@@ -9,6 +9,7 @@ MAPS = ("std_mean", "xent_mean", "cov_trace", "cov_det", "cov_det_drop_last", "e
 PLANE = {name: k for k, name in enumerate(MAPS)}
 _NEED_SM = ("std_mean", "cov_det", "cov_det_drop_last", "e_ss", "e_sy", "e_yy")
 _NEED_LOGITS = ("xent_mean", "cov_trace")
+MAX_CLASSES = 8            # MC_MAXC of csrc/mc_stats.hip: this one stays capped (the many-class entries are in many_class.py)
 
 
 def _available(has_logits, has_sm, has_gt, has_ref):
@@ -26,11 +27,19 @@ def _available(has_logits, has_sm, has_gt, has_ref):
     return out
 
 
+def check_classes(C):
+    """phx_mc_stats keeps a pixel's C x C covariance in registers: 2 <= C <= 8, said here before anything is uploaded or launched."""
+    if not 2 <= int(C) <= MAX_CLASSES:
+        raise ValueError("mc_statistics: 2 <= C <= %d classes (phx_mc_stats keeps a pixel's C x C covariance in registers), got C = %d"
+                         % (MAX_CLASSES, int(C)))
+
+
 def mc_stats_device(logits_ptr, sm_ptr, gt_ptr, sref_ptr, I, N, M, P, C, maps, stream, mean=False, amax=False):
     """Launch phx_mc_stats on `stream` over device memory: -> (maps tensor [I, 8, P] f32 or None, mean_sm tensor [I, P, C] or None,
     arg-max tensor [I, P] u8 or None), all on the device and NOT synchronised."""
     import torch
     from . import runtime as rt
+    check_classes(C)
     L = rt.lib()
     for name in maps:
         if name not in PLANE:
@@ -67,6 +76,7 @@ def mc_statistics(logits=None, sm=None, gts=None, s_ref=None, maps=None, mean=Tr
     first = logits if logits is not None else sm
     if first is None:
         raise ValueError("mc_statistics needs logits or sm")
+    check_classes(tuple(first.shape if hasattr(first, "ptr") else np.shape(first))[-1])
     on_device = hasattr(first, "ptr")
     dev = torch.device("cuda", torch.cuda.current_device())
     keep = []

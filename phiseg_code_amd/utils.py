@@ -21,9 +21,10 @@ def list_mean(lst):
 
 # ---- validation metrics (reference: utils.py:270-370, phiseg_model.py:586-613), computed by libphx on the device -----------
 def _metrics_device(samples_sm, gts, s_ref, nlabels, label0):
-    """samples_sm [I, N, X, Y, C] float32 soft-max, gts [I, M, X, Y] uint8, s_ref [I, X, Y] uint8 -> out [I, 2 + 8] float32
-    (GED, NCC, Dice per label) on the GPU; host arrays in, host array out."""
+    """samples_sm [I, N, X, Y, C] float32 soft-max, gts [I, M, X, Y] uint8, s_ref [I, X, Y] uint8 -> out [I, 2 + max(C, 8)] float32
+    (GED, NCC, Dice per label) on the GPU; host arrays in, host array out.  C <= 8: phx_validation_metrics; above: phx_metrics_wide."""
     import torch
+    from . import many_class
     from . import runtime as rt
     L = rt.lib()
     I, N, X, Y, C = samples_sm.shape
@@ -32,12 +33,17 @@ def _metrics_device(samples_sm, gts, s_ref, nlabels, label0):
     sm = torch.as_tensor(np.ascontiguousarray(samples_sm, dtype=np.float32)).to(dev)
     gt = torch.as_tensor(np.ascontiguousarray(gts, dtype=np.uint8)).to(dev)
     sr = torch.as_tensor(np.ascontiguousarray(s_ref, dtype=np.uint8)).to(dev)
-    wsb = int(L.validation_metrics_ws_bytes(I, N, M, X * Y, C))
+    wide = many_class.validation_metrics_entry(C) == "metrics_wide"
+    wsb = int((L.metrics_wide_ws_bytes if wide else L.validation_metrics_ws_bytes)(I, N, M, X * Y, C))
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    out = torch.empty(I, 10, dtype=torch.float32, device=dev)
+    out = torch.empty(I, many_class.metrics_row(C), dtype=torch.float32, device=dev)
     st = torch.cuda.current_stream().cuda_stream
-    L.validation_metrics(sm.data_ptr(), gt.data_ptr(), sr.data_ptr(), ws.data_ptr(), wsb, I, N, M, X * Y, C, label0,
-                         out.data_ptr(), st)
+    if wide:
+        L.metrics_wide(sm.data_ptr(), gt.data_ptr(), X * Y, 1, sr.data_ptr(), None, ws.data_ptr(), wsb, I, N, M, X * Y, C, label0,
+                       out.data_ptr(), st)
+    else:
+        L.validation_metrics(sm.data_ptr(), gt.data_ptr(), sr.data_ptr(), ws.data_ptr(), wsb, I, N, M, X * Y, C, label0,
+                             out.data_ptr(), st)
     return out.cpu().numpy()
 
 
