@@ -949,6 +949,60 @@ int phx_spatial_window3d(const void* src, void* dst, int dt, int B, int Ds, int 
 int phx_bn_moving_update_biased(const float* mean, const float* rstd, float eps, float* moving_mean, float* moving_var, float momentum,
                                 int C, void* stream);
 
+/* ---- the 2-D layers with explicit geometry (csrc/conv2d_pad.hip) ---------------------------------------------
+ * VALID (or SAME) padding for conv2D / dilated_conv2D / transposed_conv2D, any legal output_shape of tf.nn.conv2d_transpose, and
+ * pooling with any window.  NHWC activations, fp32 or bf16 (the dt codes); fp32 filters, fp32 accumulation; no floating-point
+ * atomics, every reduction in a fixed order: repeated calls give the same bits with or without PHX_DETERMINISTIC.  The caller passes
+ * the whole geometry -- the extent of y (Ho, Wo) and the top / left padding (pt, pl) beside kernel, stride and dilation; the kernels
+ * apply no padding rule of their own and test every index against the extents.  A non-positive extent, kernel, stride or dilation, or
+ * a negative padding, returns PHX_E_SHAPE and launches nothing.
+ *
+ * phx_conv2d_geometry: TF 1.12's rule for one convolution or pooling window, with ke = (k - 1) d + 1 per axis:
+ *   SAME   out = ceil(in / s), total = max((out - 1) s + ke - in, 0), before = total / 2
+ *   VALID  out = (in - ke) / s + 1, before = 0; in < ke is PHX_E_SHAPE
+ * tf.nn.conv2d_transpose with output extent O takes the padding of the forward convolution ON O: call it with H = O.
+ *
+ * phx_conv2d_pad_*: x [B,H,W,Cin] -> y [B,Ho,Wo,Cout], y[oy, ox] = sum over taps of x[oy sh + ky dh - pt, ox sw + kx dw - pl] w[ky][kx],
+ * filter w_hwio [kh][kw][Cin][Cout]; optional bias and activation in the forward epilogue.  dgrad writes every element of dx
+ * [B,H,W,Cin] (zeros where no output reads the input); wgrad ACCUMULATES into dw_hwio (the bias gradient is
+ * phx_channel_sum_accumulate of dy).
+ * phx_tconv2d_pad_*: x [B,H,W,Cin] -> y [B,Ho,Wo,Cout], the data gradient of the convolution above that maps [Ho,Wo] to [H,W], filter
+ * w_hwoi [kh][kw][Cout][Cin] (TF's layout); rows of y that no input reaches hold the bias only.  dgrad: dy [B,Ho,Wo,Cout] -> dx
+ * [B,H,W,Cin]; wgrad ACCUMULATES.
+ * Forward and dgrad take a vector path when the channel count they reduce over is a multiple of 4 (fp32 input) or 8 (bf16 input), for
+ * any stride and dilation: 16-byte channel reads, 8 output channels of 4 pixels per thread, the filter staged in LDS; any other count
+ * runs one thread per output element.
+ * wgrad splits the pixels of the smaller tensor (y of the convolution, x of its transpose: [B,Hs,Ws], reduced channels Ca x Cb) over
+ * blocks and sums the blocks' results in a fixed order in a second launch; ws holds phx_conv2d_pad_wgrad_ws_floats floats (0: one
+ * block per filter tile suffices, ws is not read and may be NULL), need not be cleared, and may be shared by calls on one stream. */
+enum { PHX_PAD_SAME = 0, PHX_PAD_VALID = 1 };
+int phx_conv2d_geometry(int H, int W, int kh, int kw, int sh, int sw, int dh, int dw, int padding, int* Ho, int* Wo, int* pt, int* pl);
+int phx_conv2d_pad_fwd(const void* x, int x_dt, const float* w_hwio, const float* bias, void* y, int y_dt, int B, int H, int W, int Cin,
+                       int Cout, int kh, int kw, int sh, int sw, int dh, int dw, int Ho, int Wo, int pt, int pl, int act, void* stream);
+int phx_conv2d_pad_dgrad(const void* dy, int dy_dt, const float* w_hwio, void* dx, int dx_dt, int B, int H, int W, int Cin, int Cout,
+                         int kh, int kw, int sh, int sw, int dh, int dw, int Ho, int Wo, int pt, int pl, void* stream);
+size_t phx_conv2d_pad_wgrad_ws_floats(int B, int Hs, int Ws, int Ca, int Cb, int kh, int kw);
+int phx_conv2d_pad_wgrad(const void* x, int x_dt, const void* dy, int dy_dt, float* dw_hwio, float* ws, int B, int H, int W, int Cin,
+                         int Cout, int kh, int kw, int sh, int sw, int dh, int dw, int Ho, int Wo, int pt, int pl, void* stream);
+int phx_tconv2d_pad_fwd(const void* x, int x_dt, const float* w_hwoi, const float* bias, void* y, int y_dt, int B, int H, int W, int Cin,
+                        int Cout, int kh, int kw, int sh, int sw, int dh, int dw, int Ho, int Wo, int pt, int pl, int act, void* stream);
+int phx_tconv2d_pad_dgrad(const void* dy, int dy_dt, const float* w_hwoi, void* dx, int dx_dt, int B, int H, int W, int Cin, int Cout,
+                          int kh, int kw, int sh, int sw, int dh, int dw, int Ho, int Wo, int pt, int pl, void* stream);
+int phx_tconv2d_pad_wgrad(const void* x, int x_dt, const void* dy, int dy_dt, float* dw_hwoi, float* ws, int B, int H, int W, int Cin,
+                          int Cout, int kh, int kw, int sh, int sw, int dh, int dw, int Ho, int Wo, int pt, int pl, void* stream);
+/* maxpool2D / averagepool2D with any window: x [B,H,W,C] -> y [B,Ho,Wo,C], window kh x kw, stride (sh, sw), window (oy, ox) starts at
+ * (oy sh - pt, ox sw - pl).  Padded taps take no part in a maximum; an average divides by the number of taps inside the map
+ * (tf.nn.avg_pool).  _bwd is a gather per input element over the windows that hold it, in (oy, ox) order -- windows may overlap -- and
+ * writes every element of dx; the gradient of a maximum goes to the first (row-major) maximum of its window and needs x, the average's
+ * does not read x (may be NULL).  _bwd_acc ADDS to dx (a tensor with several readers). */
+enum { PHX_POOL_MAX = 0, PHX_POOL_AVG = 1 };
+int phx_pool2d_fwd(const void* x, int dt, void* y, int mode, int B, int H, int W, int C, int kh, int kw, int sh, int sw, int pt, int pl,
+                   int Ho, int Wo, void* stream);
+int phx_pool2d_bwd(const void* x, const void* dy, int dt, void* dx, int mode, int B, int H, int W, int C, int kh, int kw, int sh, int sw,
+                   int pt, int pl, int Ho, int Wo, void* stream);
+int phx_pool2d_bwd_acc(const void* x, const void* dy, int dt, void* dx, int mode, int B, int H, int W, int C, int kh, int kw, int sh,
+                       int sw, int pt, int pl, int Ho, int Wo, void* stream);
+
 /* ---- data-parallel gradient exchange over RCCL / xGMI ------------------------------------------------
  * The reference is single-process, single-device (phiseg_model.py:151-157); the data-parallel design shards the batch over
  * ranks (one process per GPU) and exchanges ONE sum of the flat fp32 gradient arena per step.  RCCL is dlopen'ed on first use.

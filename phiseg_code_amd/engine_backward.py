@@ -429,6 +429,8 @@ class BackwardLowering:
         db = self.store.grad_ptr(b) if (b is not None and not db_done) else None
         if sv.upconv is not None:
             return self._bw_unit_upconv(op, sv, dY, db)
+        if sv.explicit is not None:
+            return self._bw_unit_explicit(op, sv, dY, db)
         if sv.volume is not None:
             return self._bw_unit_volume(op, sv, dY, db)
         if sv.general is not None:
@@ -539,12 +541,12 @@ class BackwardLowering:
             _, wd_w = self._packed(W)
             self._add_grad(xin, write_fn=lambda g: upconv.backward_data(self._emit, self._alloc, Lb, S, upc, dY, wd_w, g, B, h, w, cin, cout))
 
-    def _bw_unit_direct(self, op, sv, dY, db, wgrad, dgrad, cout=None):
-        """Filter, bias and data gradient of a unit on the direct kernels (gconv.hip / tconv.hip / conv3d.hip) with the geometry saved
-        forward."""
+    def _bw_unit_direct(self, op, sv, dY, db, wgrad, dgrad, cout=None, ws=()):
+        """Filter, bias and data gradient of a unit on the direct kernels (gconv.hip / tconv.hip / conv3d.hip / conv2d_pad.hip) with the
+        geometry saved forward.  ws: the workspace argument of a filter-gradient entry that takes one, behind dw."""
         S, x, W = self.stream, sv.x, op.attrs["W"]
         cout = cout or self._unit_dims(op, sv)[4]
-        self._emit(wgrad, x.ptr, x.dt, dY.ptr, dY.dt, self.store.grad_ptr(W), *sv.geo, S)
+        self._emit(wgrad, x.ptr, x.dt, dY.ptr, dY.dt, self.store.grad_ptr(W), *ws, *sv.geo, S)
         if db is not None:
             self._emit(self.L.channel_sum_accumulate, dY.ptr, dY.dt, db, dY.n // cout, cout, S)
         if self.req.get(op.inputs[0], False):
@@ -557,6 +559,25 @@ class BackwardLowering:
         Lb = self.L
         wgrad, dgrad = (Lb.gconv3d_wgrad, Lb.gconv3d_dgrad) if sv.volume[0] == "conv" else (Lb.tconv3d_wgrad, Lb.tconv3d_dgrad)
         self._bw_unit_direct(op, sv, dY, db, wgrad, dgrad, cout=sv.geo[5])
+
+    def _bw_unit_explicit(self, op, sv, dY, db):
+        """conv2d_pad.hip: the filter gradient sums the pixels of the smaller tensor (the convolution's output, the transposed
+        convolution's input) per block and adds the blocks' sums in a second launch, through a workspace of the plan's."""
+        Lb, conv = self.L, sv.explicit == "conv"
+        B, H, Wd, cin, cout, kh, kw = sv.geo[:7]
+        Ho, Wo = sv.geo[11:13]
+        small = (B, Ho, Wo, cin, cout) if conv else (B, H, Wd, cout, cin)
+        n = int(Lb.conv2d_pad_wgrad_ws_floats(*small, kh, kw))
+        ws = self._alloc((n,), F32).ptr if n else None
+        wgrad, dgrad = (Lb.conv2d_pad_wgrad, Lb.conv2d_pad_dgrad) if conv else (Lb.tconv2d_pad_wgrad, Lb.tconv2d_pad_dgrad)
+        self._bw_unit_direct(op, sv, dY, db, wgrad, dgrad, cout=cout, ws=(ws,))
+
+    def _bw_pool2d(self, op):
+        x, d = self.val[op.inputs[0]], self.grad[op.outputs[0]]
+        args = self._pool2d_args(op, x)
+        self._add_grad(op.inputs[0], write_fn=lambda g: self._emit(self.L.pool2d_bwd, x.ptr, d.ptr, d.dt, g.ptr, *args, self.stream),
+                       accum_fn=(lambda g: self._emit(self.L.pool2d_bwd_acc, x.ptr, d.ptr, d.dt, g.ptr, *args, self.stream))
+                       if d.dt == x.dt else None)
 
     def _bw_unit_transposed(self, op, sv, dY, db):
         self._bw_unit_direct(op, sv, dY, db, self.L.tconv2d_wgrad, self.L.tconv2d_dgrad)

@@ -229,10 +229,11 @@ class StatsSource(enum.Enum):
 class ConvSaved:
     """What the forward lowering of a conv_unit / transposed / general unit / norm_act leaves for the backward pass (Plan.saved[op]).
     An unknown attribute raises on read and on write.  volume: the (form, kd, kh, kw, sd, sh, sw) geometry of a 3-D unit (("norm",) on a
-    norm_act over a 5-D tensor), whose x / out are 5-D and whose y is kept folded to [B, D H, W, C].  renorm: a training-mode batch-renorm layer's RenormSaved, None otherwise."""
+    norm_act over a 5-D tensor), whose x / out are 5-D and whose y is kept folded to [B, D H, W, C].  renorm: a training-mode batch-renorm layer's RenormSaved, None otherwise.
+    explicit: the form ("conv" | "tconv") of a 2-D unit lowered with its whole geometry (csrc/conv2d_pad.hip), whose geo carries it."""
     _OPTIONAL = dict(route=NormRoute.NONE, y=None, scale=None, shift=None, mean=None, rstd=None, NS=None, P=None, G=None, wd_pad=None,
                      upconv=None, a_unwritten=None, fsums=None, fpivot=None, transposed=None, general=None, volume=None, geo=None, f32m=False,
-                     norm_head=False, latent=False, renorm=None)
+                     norm_head=False, latent=False, renorm=None, explicit=None)
     __slots__ = ("x", "out", "norm", "mfma", "padded", "cin_eff", "k1", "head1x1") + tuple(_OPTIONAL)
 
     def __init__(self, x, out, norm, mfma, padded, cin_eff, k1, head1x1, **optional):

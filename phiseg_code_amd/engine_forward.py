@@ -130,7 +130,7 @@ class ForwardLowering:
                 and len(va.shape) == 4 and va.shape[-1] % 32 == 0 and vb.shape[-1] % 32 == 0 and len(cons) == 1 and ot not in self.fetches):
             c = cons[0]
             ca = c.attrs if c.type == "conv_unit" else None
-            if (ca is not None and ca["ksize"] == 3 and ca.get("transposed") is None and ca.get("general") is None and ca.get("volume") is None
+            if (ca is not None and ca["ksize"] == 3 and ca.get("transposed") is None and ca.get("general") is None and ca.get("volume") is None and ca.get("explicit") is None
                     and ca["W"].shape[-1] % 32 == 0 and self.op_lane.get(c) == self.op_lane.get(op) and c not in self._lat):
                 # concat-free: the one reader, a 3x3 convolution on the MFMA path, takes the two tensors as they are (no launch here)
                 self.val[ot] = DualBuf(va, vb)
@@ -286,8 +286,14 @@ class ForwardLowering:
         W, b = a["W"], a["b"]
         B, H, Wd = x.shape[0], x.shape[1], x.shape[2]
         S, Lb = self.stream, self.L
-        vol = a.get("volume")
-        if vol is not None:
+        vol, exp = a.get("volume"), a.get("explicit")
+        if exp is not None:
+            # a 2-D unit with its whole geometry on the kernels of csrc/conv2d_pad.hip (VALID padding, a free output_shape of the
+            # transposed layer): filter HWIO (form "conv") / HWOI ("tconv"), geo = (B, H, W, Cin, Cout, kh, kw, sh, sw, dh, dw, Ho, Wo, pt, pl)
+            cin, cout = (W.shape[2], W.shape[3]) if exp[0] == "conv" else (W.shape[3], W.shape[2])
+            geo = (B, H, Wd, cin, cout) + tuple(exp[1:])
+            conv_fwd = Lb.conv2d_pad_fwd if exp[0] == "conv" else Lb.tconv2d_pad_fwd
+        elif vol is not None:
             # conv3D / transposed_conv3D on the kernels of csrc/conv3d.hip: x is [B, D, H, W, C], filter DHWIO / DHWOI
             form = vol[0]
             cin, cout = (W.shape[3], W.shape[4]) if form == "conv" else (W.shape[4], W.shape[3])
@@ -310,7 +316,8 @@ class ForwardLowering:
         training = a["training"] if isinstance(a["training"], bool) else self.training
         norm = self._lowered_norm(a, training)
         wptr, bptr = self.store.ptr(W), (self.store.ptr(b) if b is not None else None)
-        sv = self.saved[op] = ConvSaved.plain(x, out, norm, cin, transposed=a.get("transposed"), general=a.get("general"), volume=vol, geo=geo)
+        sv = self.saved[op] = ConvSaved.plain(x, out, norm, cin, transposed=a.get("transposed"), general=a.get("general"), volume=vol, geo=geo,
+                                              explicit=exp[0] if exp is not None else None)
         if norm is None:
             self._emit(conv_fwd, x.ptr, x.dt, wptr, bptr, out.ptr, out.dt, *geo, act, S)
             return
@@ -345,7 +352,7 @@ class ForwardLowering:
 
         def is_head(op, act):
             a = op.attrs
-            if op.type != "conv_unit" or a.get("transposed") is not None or a.get("general") is not None or a.get("volume") is not None:
+            if op.type != "conv_unit" or a.get("transposed") is not None or a.get("general") is not None or a.get("volume") is not None or a.get("explicit") is not None:
                 return False
             W = a["W"]
             return (a["ksize"] == 1 and a["norm"] is None and a["b"] is not None and a["act"] == act and W.shape[-1] in (2, 4, 6)
@@ -412,7 +419,7 @@ class ForwardLowering:
 
         def plain_1x1(op):
             a = op.attrs
-            return (op.type == "conv_unit" and a.get("transposed") is None and a.get("general") is None and a.get("volume") is None and a["ksize"] == 1
+            return (op.type == "conv_unit" and a.get("transposed") is None and a.get("general") is None and a.get("volume") is None and a.get("explicit") is None and a["ksize"] == 1
                     and op not in self._lat)
         for tb in ops:
             if tb.type != "tile_batch" or len(tb.inputs[0].shape) != 4:
@@ -510,7 +517,7 @@ class ForwardLowering:
         if len(cons) != 1 or cons[0].type != "conv_unit" or cons[0] in self._lat:
             return None
         c, ca = cons[0], cons[0].attrs
-        if (ca.get("transposed") is not None or ca.get("general") is not None or ca.get("volume") is not None or ca["ksize"] != 1 or ca["norm"] is not None
+        if (ca.get("transposed") is not None or ca.get("general") is not None or ca.get("volume") is not None or ca.get("explicit") is not None or ca["ksize"] != 1 or ca["norm"] is not None
                 or ca["b"] is None or ca["act"] != "identity" or c.inputs[0] is not out or c.outputs[0].kind != G.KIND_F32
                 or c.outputs[0] in self.fetches or self.op_lane.get(c) != self.op_lane.get(op)):
             return None
@@ -530,7 +537,7 @@ class ForwardLowering:
             return False
         for c in cons:
             ca = c.attrs
-            if (c.type != "conv_unit" or c in self._lat or ca.get("transposed") is not None or ca.get("general") is not None or ca.get("volume") is not None
+            if (c.type != "conv_unit" or c in self._lat or ca.get("transposed") is not None or ca.get("general") is not None or ca.get("volume") is not None or ca.get("explicit") is not None
                     or ca["ksize"] != 3 or ca["norm"] != "batch" or ca["b"] is not None or c.inputs[0] is not out):
                 return False
             tr = ca["training"] if isinstance(ca["training"], bool) else self.training
@@ -543,7 +550,7 @@ class ForwardLowering:
     def _fw_conv_unit(self, op, bw):
         """conv -> [bias] -> [norm] -> act: prepare the operands, choose the normalisation route (conv_norm_route), emit that route."""
         a = op.attrs
-        if a.get("transposed") is not None or a.get("general") is not None or a.get("volume") is not None:
+        if a.get("transposed") is not None or a.get("general") is not None or a.get("volume") is not None or a.get("explicit") is not None:
             return self._fw_tconv_unit(op, bw)
         if op in self._norm_head:                # its forward ran inside the producer's apply pass
             self.saved[op] = ConvSaved.plain(self.val[op.inputs[0]], self.val[op.outputs[0]], None, a["W"].shape[-2], head1x1=True, norm_head=True)
@@ -863,6 +870,18 @@ class ForwardLowering:
         self.val[op.outputs[0]] = out
         self._emit(self.L.maxpool2x2_fwd, x.ptr, x.dt, out.ptr, x.shape[0], x.shape[1], x.shape[2], x.shape[3], self.stream)
 
+    @staticmethod
+    def _pool2d_args(op, x):
+        """(mode, B, H, W, C, kh, kw, sh, sw, pt, pl, Ho, Wo) of a pool2d node on its input buffer"""
+        a, o = op.attrs, op.outputs[0].shape
+        return ({"max": 0, "avg": 1}[a["mode"]], *x.shape, *a["window"], *a["strides"], *a["pad"], o[1], o[2])
+
+    def _fw_pool2d(self, op, bw):
+        x = self.val[op.inputs[0]]
+        out = self._alloc(self._cshape(op.outputs[0]), x.dt)
+        self.val[op.outputs[0]] = out
+        self._emit(self.L.pool2d_fwd, x.ptr, x.dt, out.ptr, *self._pool2d_args(op, x), self.stream)
+
     def _fw_max_pool3d(self, op, bw):
         x = self.val[op.inputs[0]]
         out = self._alloc(self._cshape(op.outputs[0]), x.dt)
@@ -1000,7 +1019,7 @@ class ForwardLowering:
             return None
         c = cons[0]
         a = c.attrs if c.type == "conv_unit" else None
-        if (a is None or c.inputs[0] is not ot or a["ksize"] != 3 or a.get("transposed") is not None or a.get("general") is not None or a.get("volume") is not None
+        if (a is None or c.inputs[0] is not ot or a["ksize"] != 3 or a.get("transposed") is not None or a.get("general") is not None or a.get("volume") is not None or a.get("explicit") is not None
                 or a["norm"] not in ("batch", "group", "instance") or (a["norm"] == "batch") != (a["b"] is None)
                 or self.op_lane.get(c) != self.op_lane.get(op) or c in self._lat):
             return None

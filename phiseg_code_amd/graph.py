@@ -219,8 +219,54 @@ def random_normal(like, stream):
     return get_default_graph().add_op("random_normal", [like], dict(stream=int(stream)), [(like.shape, KIND_F32)])[0]
 
 
+def conv_geometry(h, w, kernel_size, strides, dilations=(1, 1), padding="SAME"):
+    """TF 1.12's rule for one convolution or pooling window (phx_conv2d_geometry is the same rule in C) -> (Ho, Wo, pt, pl).  With the
+    effective extent ke = (k - 1) d + 1 per axis, SAME: out = ceil(in / s), total = max((out - 1) s + ke - in, 0), before = total // 2;
+    VALID: out = (in - ke) // s + 1, no padding, and in < ke is a ValueError (TF refuses a negative dimension when the graph is built)."""
+    if padding not in ("SAME", "VALID"):
+        raise ValueError("padding must be 'SAME' or 'VALID', got %r" % (padding,))
+    out, before = [], []
+    for n, k, s, d in zip((int(h), int(w)), kernel_size, strides, dilations):
+        n, k, s, d = int(n), int(k), int(s), int(d)
+        if n < 1 or k < 1 or s < 1 or d < 1:
+            raise ValueError("conv_geometry: extents, kernel, strides and dilations must be positive")
+        ke = (k - 1) * d + 1
+        if padding == "VALID":
+            if n < ke:
+                raise ValueError("VALID padding: an input extent of %d is smaller than the window extent %d (negative output size)" % (n, ke))
+            out.append((n - ke) // s + 1)
+            before.append(0)
+        else:
+            o = -(-n // s)
+            out.append(o)
+            before.append(max((o - 1) * s + ke - n, 0) // 2)
+    return out[0], out[1], before[0], before[1]
+
+
+def conv_transpose_geometry(h, w, kernel_size, strides, padding="SAME", output_hw=None):
+    """tf.nn.conv2d_transpose of an [h, w] input -> (Ho, Wo, pt, pl).  An output extent O is legal iff the forward convolution of O gives
+    the input extent n -- SAME: ceil(O / s) == n; VALID: O in [(n - 1) s + k, (n - 1) s + k + s - 1] -- and the padding is that
+    convolution's on O.  output_hw None is the reference's n * s (under VALID legal only for k <= s).  An illegal one is a ValueError
+    that names the legal range."""
+    if padding not in ("SAME", "VALID"):
+        raise ValueError("padding must be 'SAME' or 'VALID', got %r" % (padding,))
+    res = []
+    for ax, (n, k, s) in enumerate(zip((int(h), int(w)), kernel_size, strides)):
+        n, k, s = int(n), int(k), int(s)
+        O = n * s if output_hw is None else int(output_hw[ax])
+        lo, hi = ((n - 1) * s + 1, n * s) if padding == "SAME" else ((n - 1) * s + k, (n - 1) * s + k + s - 1)
+        if not lo <= O <= hi:
+            raise ValueError("conv2d_transpose (%s, kernel %d, stride %d): an output extent of %d%s does not map back to the input extent %d; "
+                             "legal output extents are %d..%d -- pass output_shape" % (padding, k, s, O, "" if output_hw is not None else
+                                                                                      " (input * strides, the default)", n, lo, hi))
+        res.append(O)
+    ho, wo, pt, pl = conv_geometry(res[0], res[1], kernel_size, strides, (1, 1), padding)
+    assert (ho, wo) == (int(h), int(w))
+    return res[0], res[1], pt, pl
+
+
 def conv_unit(x, W, b, ksize, norm, norm_vars, act, training, num_groups=None, head=False, name="conv", transposed=None,
-              general=None, volume=None):
+              general=None, volume=None, explicit=None):
     """conv (SAME, stride 1) -> [+bias] -> [norm] -> act as ONE node (tfwrapper/layers.py:122-135).
     transposed = (kh, kw, sh, sw): tf.nn.conv2d_transpose instead (layers.py:197-258), W is [kh, kw, Cout, Cin] and the output
     is sh x sw times larger.  general = (kh, kw, sh, sw, dh, dw): strided / dilated SAME convolution (conv2D with strides,
@@ -228,10 +274,24 @@ def conv_unit(x, W, b, ksize, norm, norm_vars, act, training, num_groups=None, h
     output is ceil(H / sh) x ceil(W / sw).  volume = (form, kd, kh, kw, sd, sh, sw) on a 5-D [B, D, H, W, C] input (csrc/conv3d.hip):
     form "conv" is tf.nn.conv3d with W [kd, kh, kw, Cin, Cout] and output ceil(D / sd) x ceil(H / sh) x ceil(W / sw) (conv3D,
     layers.py:148-194), form "tconv" tf.nn.conv3d_transpose with W [kd, kh, kw, Cout, Cin] and output D sd x H sh x W sw
-    (transposed_conv3D, layers.py:261-323)."""
+    (transposed_conv3D, layers.py:261-323).  explicit = (form, kh, kw, sh, sw, dh, dw, Ho, Wo, pt, pl): a 2-D unit with its whole geometry
+    -- output extent and top / left padding from conv_geometry / conv_transpose_geometry -- on the kernels of csrc/conv2d_pad.hip: form
+    "conv" with W [kh, kw, Cin, Cout] (VALID padding of conv2D / dilated_conv2D), form "tconv" with W [kh, kw, Cout, Cin]
+    (transposed_conv2D under VALID padding or with an output_shape other than input * strides)."""
     kind = KIND_F32 if head else KIND_ACT
     attrs = dict(W=W, b=b, ksize=int(ksize), norm=norm, norm_vars=norm_vars, act=act, training=training,
                  num_groups=num_groups, head=head, transposed=transposed, general=general, volume=volume)
+    if explicit is not None:
+        # (the key exists only on the units that use it: every other unit keeps the attributes it has always had)
+        if len(x.shape) != 4 or len(W.shape) != 4 or len(explicit) != 11 or explicit[0] not in ("conv", "tconv") \
+                or transposed is not None or general is not None or volume is not None:
+            raise ValueError("conv_unit: explicit = ('conv' | 'tconv', kh, kw, sh, sw, dh, dw, Ho, Wo, pt, pl) takes a 4-D input and a 4-D filter")
+        explicit = (explicit[0],) + tuple(int(v) for v in explicit[1:])
+        if tuple(W.shape[:2]) != explicit[1:3] or W.shape[3 if explicit[0] == "tconv" else 2] != x.shape[3]:
+            raise ValueError("conv_unit: filter %s does not fit the explicit geometry %s on %r" % (W.shape, explicit, x))
+        attrs["explicit"] = explicit
+        shape = (x.shape[0], explicit[7], explicit[8], W.shape[2 if explicit[0] == "tconv" else 3])
+        return get_default_graph().add_op("conv_unit", [x], attrs, [(shape, kind)], name=name)[0]
     if volume is not None:
         if len(x.shape) != 5 or len(W.shape) != 5 or volume[0] not in ("conv", "tconv") or transposed is not None or general is not None:
             raise ValueError("conv_unit: volume = ('conv' | 'tconv', kd, kh, kw, sd, sh, sw) takes a 5-D input and a 5-D filter")
@@ -264,6 +324,20 @@ def max_pool2x2(x):
     """tf.nn.max_pool 2x2 / stride 2 / SAME (tfwrapper/layers.py:18-28)."""
     n, h, w, c = x.shape
     return get_default_graph().add_op("maxpool", [x], {}, [((n, (h + 1) // 2, (w + 1) // 2, c), x.kind)])[0]
+
+
+def pool2d(x, mode, kernel_size=(2, 2), strides=(2, 2), padding="SAME"):
+    """tf.nn.max_pool / tf.nn.avg_pool with any window, stride and padding (tfwrapper/layers.py:18-28, 44-54) on csrc/conv2d_pad.hip:
+    padded taps take no part in a maximum, an average divides by the number of taps inside the map."""
+    if mode not in ("max", "avg"):
+        raise ValueError("pool2d: mode 'max' or 'avg', got %r" % (mode,))
+    if len(x.shape) != 4 or len(kernel_size) != 2 or len(strides) != 2:
+        raise ValueError("pool2d: a [B, H, W, C] tensor and two-entry kernel_size / strides are expected")
+    n, h, w, c = x.shape
+    k, s = tuple(int(v) for v in kernel_size), tuple(int(v) for v in strides)
+    ho, wo, pt, pl = conv_geometry(h, w, k, s, (1, 1), padding)
+    return get_default_graph().add_op("pool2d", [x], dict(mode=mode, window=k, strides=s, pad=(pt, pl)), [((n, ho, wo, c), x.kind)],
+                                      name=mode + "pool2d")[0]
 
 
 def max_pool3d(x, window=(2, 2, 2)):

@@ -10,7 +10,11 @@ and the 3-D family -- ``conv3D``, ``transposed_conv3D``, ``maxpool3D``, ``biline
 tfnorm.batch_norm; what a layer does not support raises NotImplementedError with the reason.  Every ``activation=`` also takes
 ``activations.leaky_relu`` (or a ``functools.partial`` of it with ``alpha``): the unit then carries the identity and a
 ``graph.leaky_relu`` node follows it; ``normalise_post_activation=True`` is the unit without normalisation followed by a
-normalisation node (``_unit``).
+normalisation node (``_unit``).  The 2-D convolutions and pools take ``padding="VALID"`` as well as ``"SAME"``,
+``transposed_conv2D`` any legal ``output_shape``, and the pools any window and strides: such a call builds a unit (or a ``pool2d``
+node) that carries its whole geometry, by TF 1.12's rule (``graph.conv_geometry``), and runs on csrc/conv2d_pad.hip; what TF refuses
+when the graph is built -- an input smaller than the window under VALID, an output shape the forward convolution does not map back to
+the input -- is a ValueError here too.  Calls with the values accepted before build the nodes they always built.
 """
 import logging
 
@@ -26,10 +30,12 @@ STANDARD_NONLINEARITY = activations.relu
 
 
 def averagepool2D(x, kernel_size=(2, 2), strides=(2, 2), padding="SAME"):
-    """tf.nn.avg_pool 2x2 / stride 2 / SAME (odd sizes: divide by the number of valid taps)."""
-    if tuple(kernel_size) != (2, 2) or tuple(strides) != (2, 2) or padding != "SAME":
-        raise NotImplementedError("only the 2x2 / stride 2 / SAME average pool is on the hot path")
-    return G.avg_pool2x2(x)
+    """tf.nn.avg_pool (tfwrapper/layers.py:44-54): any window, strides and padding ("SAME" | "VALID"); a window that reaches into the
+    padding divides by the number of taps inside the map.  The default 2x2 / stride 2 / SAME is the hot path's own node; anything else
+    is a graph.pool2d node (csrc/conv2d_pad.hip)."""
+    if tuple(kernel_size) == (2, 2) and tuple(strides) == (2, 2) and padding == "SAME":
+        return G.avg_pool2x2(x)
+    return G.pool2d(x, "avg", kernel_size, strides, padding)
 
 
 def global_averagepool2D(x, name=None):
@@ -73,6 +79,20 @@ def _unit(x, weights, biases, ksize, kind, norm_vars, activation, training, num_
     return _leaky(op, alpha)
 
 
+def _valid_geometry(x, what, kernel_size, strides, dilations, padding):
+    """None under SAME padding (the layer keeps the unit form it has always built); under VALID the `explicit` geometry of
+    graph.conv_unit, form "conv", from graph.conv_geometry."""
+    if padding == "SAME":
+        return None
+    if padding != "VALID":
+        raise ValueError("%s: padding must be 'SAME' or 'VALID', got %r" % (what, padding))
+    shp = x.get_shape().as_list()
+    if len(shp) != 4:
+        raise ValueError("%s: a [B, H, W, C] tensor is expected, got %s" % (what, shp))
+    k, s, d = (tuple(int(v) for v in t) for t in (kernel_size, strides, dilations))
+    return ("conv",) + k + s + d + G.conv_geometry(shp[1], shp[2], k, s, d, "VALID")
+
+
 def conv2D(x,
            name,
            kernel_size=(3, 3),
@@ -87,13 +107,14 @@ def conv2D(x,
            add_bias=True,
            **kwargs):
     """Standard 2-D convolutional layer: conv -> [bias] -> normalisation -> activation (normalise_post_activation: activation ->
-    normalisation) [-> dropout].  kwargs can carry ``training`` and normalisation parameters (``num_groups``)."""
-    if padding != "SAME":
-        raise NotImplementedError("conv2D: SAME padding (the only value the reference's call sites use)")
+    normalisation) [-> dropout].  kwargs can carry ``training`` and normalisation parameters (``num_groups``).  padding "SAME" or
+    "VALID" (out = (in - k) // s + 1, no padding: the unpadded convolutions of the classic U-Net, on csrc/conv2d_pad.hip); an input
+    smaller than the kernel under VALID is a ValueError."""
+    explicit = _valid_geometry(x, "conv2D", kernel_size, strides, (1, 1), padding)
     # stride 1 with a 1x1 / 3x3 kernel is the hot path (MFMA / direct / head kernels); anything else -- strided convolutions of the
     # residual units, larger kernels -- runs on the general direct kernels of csrc/gconv.hip
     general = None
-    if tuple(strides) != (1, 1) or tuple(kernel_size) not in ((1, 1), (3, 3)):
+    if explicit is None and (tuple(strides) != (1, 1) or tuple(kernel_size) not in ((1, 1), (3, 3))):
         general = (int(kernel_size[0]), int(kernel_size[1]), int(strides[0]), int(strides[1]), 1, 1)
     _check_callables(normalisation, activation)
 
@@ -117,9 +138,10 @@ def conv2D(x,
         norm_vars = tfnorm.make_variables(kind, num_filters)
         training = kwargs.get('training', True)
         # heads (mu / sigma / logits) keep fp32 storage in the bf16 configuration
-        head = kind is None and activation is not activations.relu and general is None
+        head = kind is None and activation is not activations.relu and general is None and explicit is None
+        geometry = dict(general=general) if explicit is None else dict(explicit=explicit)
         op = _unit(x, weights, biases, kernel_size[0], kind, norm_vars, activation, training, kwargs.get('num_groups'), head, 'conv',
-                   post=normalise_post_activation, general=general)
+                   post=normalise_post_activation, **geometry)
         if dropout_p is not None:
             op = dropout(op, keep_prob=dropout_p, training=training)
         return op
@@ -140,9 +162,8 @@ def dilated_conv2D(bottom,
                    **kwargs):
     """tfwrapper/layers.py:378-425: tf.nn.atrous_conv2d(bottom, W, rate, SAME) -> [bias] -> normalisation -> activation
     (normalise_post_activation: activation -> normalisation) [-> dropout].  (Unlike conv2D the bias is kept in front of batch_norm,
-    layers.py:406-409.)"""
-    if padding != "SAME":
-        raise NotImplementedError("dilated_conv2D: SAME padding")
+    layers.py:406-409.)  padding "SAME" or "VALID": the output shrinks by (k - 1) * rate per axis under VALID."""
+    explicit = _valid_geometry(bottom, "dilated_conv2D", kernel_size, (1, 1), (rate, rate), padding)
     _check_callables(normalisation, activation)
     cin = bottom.get_shape().as_list()[3]
     g = G.get_default_graph()
@@ -153,9 +174,10 @@ def dilated_conv2D(bottom,
         kind = tfnorm.KIND[normalisation]
         norm_vars = tfnorm.make_variables(kind, num_filters)
         training = kwargs.get('training', True)
+        geometry = dict(explicit=explicit) if explicit is not None else \
+            dict(general=(int(kernel_size[0]), int(kernel_size[1]), 1, 1, int(rate), int(rate)))
         op = _unit(bottom, weights, biases, kernel_size[0], kind, norm_vars, activation, training, kwargs.get('num_groups'), False,
-                   'atrous', post=normalise_post_activation,
-                   general=(int(kernel_size[0]), int(kernel_size[1]), 1, 1, int(rate), int(rate)))
+                   'atrous', post=normalise_post_activation, **geometry)
         if dropout_p is not None:
             op = dropout(op, keep_prob=dropout_p, training=training)
         return op
@@ -301,10 +323,12 @@ def reshape_pool2D_layer(x):
 
 
 def maxpool2D(x, kernel_size=(2, 2), strides=(2, 2), padding="SAME"):
-    """tf.nn.max_pool 2x2 / stride 2 / SAME (tfwrapper/layers.py:18-28)."""
-    if tuple(kernel_size) != (2, 2) or tuple(strides) != (2, 2) or padding != "SAME":
-        raise NotImplementedError("maxpool2D: 2x2 / stride 2 / SAME (the reference's defaults)")
-    return G.max_pool2x2(x)
+    """tf.nn.max_pool (tfwrapper/layers.py:18-28): any window, strides and padding ("SAME" | "VALID"); padded taps take no part in the
+    maximum and the gradient goes to the first maximum of a window in row-major order.  The reference's default 2x2 / stride 2 / SAME
+    keeps its own node; anything else is a graph.pool2d node (csrc/conv2d_pad.hip)."""
+    if tuple(kernel_size) == (2, 2) and tuple(strides) == (2, 2) and padding == "SAME":
+        return G.max_pool2x2(x)
+    return G.pool2d(x, "max", kernel_size, strides, padding)
 
 
 def pad_to_size(bottom, output_size):
@@ -343,13 +367,19 @@ def transposed_conv2D(bottom,
     """Standard 2-D transposed convolution (tfwrapper/layers.py:197-258): tf.nn.conv2d_transpose with a [kh, kw, num_filters,
     bottom channels] filter, default behaviour up-samples by a factor of 2; -> [bias] -> normalisation -> activation
     (normalise_post_activation: activation -> normalisation) [-> dropout].  Unlike conv2D the reference keeps the bias here even in
-    front of batch_norm (layers.py:231-234)."""
-    if padding != "SAME":
-        raise NotImplementedError("transposed_conv2D: SAME padding (the reference's default) only")
+    front of batch_norm (layers.py:231-234).  padding "SAME" or "VALID".  output_shape None is input * strides as in the reference (under
+    VALID legal only for kernel <= stride, e.g. the 2x2 / stride 2 up-convolution of the classic U-Net); an explicit output_shape
+    [B, Ho, Wo, C] may be any extent the forward convolution maps back to the input -- SAME: ceil(O / s) == n; VALID: O in
+    [(n - 1) s + k, (n - 1) s + k + s - 1] -- and anything else is a ValueError that names the legal range.  Rows of the output that no
+    input reaches hold the bias only."""
     _check_callables(normalisation, activation)
     shp = bottom.get_shape().as_list()
-    if output_shape is not None and tuple(output_shape[1:3]) != (shp[1] * strides[0], shp[2] * strides[1]):
-        raise NotImplementedError("transposed_conv2D: output_shape other than input * strides")
+    k, st = tuple(int(v) for v in kernel_size), tuple(int(v) for v in strides)
+    explicit = None
+    if padding != "SAME" or (output_shape is not None and tuple(output_shape[1:3]) != (shp[1] * st[0], shp[2] * st[1])):
+        # (SAME with the default extent keeps the unit form it has always built, on csrc/tconv.hip)
+        out_hw = None if output_shape is None else tuple(int(v) for v in output_shape[1:3])
+        explicit = ("tconv",) + k + st + (1, 1) + G.conv_transpose_geometry(shp[1], shp[2], k, st, padding, out_hw)
     weight_shape = [kernel_size[0], kernel_size[1], num_filters, shp[3]]
     g = G.get_default_graph()
     with g.variable_scope(name):
@@ -358,9 +388,9 @@ def transposed_conv2D(bottom,
         kind = tfnorm.KIND[normalisation]
         norm_vars = tfnorm.make_variables(kind, num_filters)
         training = kwargs.get('training', True)
+        geometry = dict(explicit=explicit) if explicit is not None else dict(transposed=k + st)
         op = _unit(bottom, weights, biases, kernel_size[0], kind, norm_vars, activation, training, kwargs.get('num_groups'), False,
-                   'deconv', post=normalise_post_activation,
-                   transposed=(int(kernel_size[0]), int(kernel_size[1]), int(strides[0]), int(strides[1])))
+                   'deconv', post=normalise_post_activation, **geometry)
         if dropout_p is not None:
             op = dropout(op, keep_prob=dropout_p, training=training)
         return op
