@@ -872,6 +872,48 @@ int phx_augment_batch_nearest(const float* images, const unsigned char* labels, 
                               float* x_out, unsigned char* s_out, void* workspace, size_t workspace_bytes, int B, int X, int Y, int A,
                               int nlabels, void* stream);
 
+/* ---- multi-channel images (exp_config.image_size = (H, W, Cx), 2 <= Cx <= 16; csrc/multichannel.hip) -------------
+ * The entries above that meet the image as an array of pixels -- phx_posterior_input, the three producers, PHX_GRID_IMAGE_F32 of
+ * phx_summary_grid_u8 -- keep their one-channel contract; these take the channel-interleaved image [..][Cx] for 2 <= Cx <= 16 and
+ * REFUSE Cx = 1 (PHX_E_SHAPE), so that a channel count has exactly one entry.  16 is a choice, not a measurement.  Every entry
+ * validates first and launches nothing on a bad argument, allocates nothing, never synchronises, and uses no floating-point atomics.
+ *
+ * phx_posterior_input_mc: x [npix][Cx] f32, s [npix] u8 -> out [npix][Cx + nlabels] (out_dt PHX_F32 or PHX_BF16, round to nearest even):
+ * out[p][:Cx] = x[p][:], out[p][Cx + c] = (c == s[p] ? 1 : 0) - 0.5; a label >= nlabels gives an all -0.5 row, as phx_posterior_input
+ * does.  1 <= nlabels <= 256, npix < 2^40 (else PHX_E_SHAPE); a null pointer or another out_dt is PHX_E_INVAL.  No alignment is
+ * required of any pointer beyond that of its element type. */
+int phx_posterior_input_mc(const float* x, const uint8_t* s, void* out, int out_dt, size_t npix, int Cx, int nlabels, void* stream);
+/* phx_augment_batch_mc: the mini-batch producer for images [N][X][Y][Cx] f32, labels [N][X][Y][A] u8 -> x_out [B][X][Y][Cx] f32,
+ * s_out [B][X][Y] u8 (a plan's x_input / s_input buffers can be written directly).  params_dev: the SAME B records as above
+ * (phx_augment_param_bytes, same flags).  ONE entry for the four single-channel forms:
+ *   ctrl_dev NULL              the plain producer (a record's elastic bit is not read), as phx_augment_batch
+ *   ctrl_dev [B][2][3][3] f64  the elastic producer for the records that carry bit 16, as phx_augment_batch_elastic
+ *   1 <= nlabels <= 4          label maps as one-hot planes interpolated in double and arg-maxed
+ *   5 <= nlabels <= 256        label maps through the nearest-neighbour chain, as phx_augment_batch_nearest
+ * Every image channel is resampled with the coordinates and weights of the single-channel path, in its operation order and without
+ * FMA contraction -- what OpenCV does with a multi-channel Mat in warpAffine / resize / remap.  Where the reference's own
+ * _augmentation_function stops on a 3-D image (`n_x, n_y = img.shape` in its crop-scale and elastic branches), this per-channel rule
+ * IS the definition.  The OpenCV rules are restated from its published algorithms -- BELIEVED, NOT EXECUTABLE HERE (OpenCV is not
+ * installed), the standing of the entries above.  The label map does not depend on the image and equals what the single-channel
+ * entries give for the same records; a channel equals what they give for that channel as a plane.
+ * One block per (output image, channel), the intermediate one fp32 plane in LDS: X * Y * 4 <= 160 KiB, as above.  workspace:
+ * phx_augment_batch_mc_ws_bytes(B, X, Y, Cx, nlabels, elastic = ctrl_dev != NULL) bytes, 4-byte aligned; 0 (may be NULL) without the
+ * elastic stage or where a block's intermediates fit LDS (9 X Y bytes with nlabels <= 4, 8 X Y above), else [B][Cx][X][Y] f32 and,
+ * with nlabels <= 4, [B][X][Y] u8 behind it.
+ * Refusals: Cx outside 2 .. 16, nlabels outside 1 .. 256, X * Y * 4 > 160 KiB, a non-positive X / Y / A: PHX_E_SHAPE; a null
+ * pointer, a workspace that is missing, misaligned or too small: PHX_E_INVAL.  B <= 0 launches nothing and is PHX_OK. */
+size_t phx_augment_batch_mc_ws_bytes(int B, int X, int Y, int Cx, int nlabels, int elastic);
+int phx_augment_batch_mc(const float* images, const unsigned char* labels, const void* params_dev, const double* ctrl_dev, float* x_out,
+                         unsigned char* s_out, void* workspace, size_t workspace_bytes, int B, int X, int Y, int A, int Cx, int nlabels,
+                         void* stream);
+/* phx_summary_grid_image_mc: put_kernels_on_grid of an image batch src [B][H][W][Cx] f32 -> out [(H + 2) * grid_y][(W + 2) * grid_x][Cout]
+ * u8, channels 0 .. Cout - 1 of src, Cout in {1, 3, 4} and Cout <= Cx.  Tile placement and pixel rule of PHX_GRID_IMAGE_F32 above:
+ * (v - min) / max * 254 in fp32, truncated, NaN -> 0, saturating; min / max over the WHOLE tensor, all Cx channels (as
+ * put_kernels_on_grid reduces it), reduced in this call.  work: PHX_SUMMARY_GRID_WS_BYTES bytes.  grid_y * grid_x != B, a bad Cx or
+ * Cout: PHX_E_SHAPE; a null pointer: PHX_E_INVAL. */
+int phx_summary_grid_image_mc(const float* src, int B, int H, int W, int Cx, int Cout, int grid_y, int grid_x, unsigned char* out, void* work,
+                              void* stream);
+
 
 /* ---- layer normalisation (tfwrapper/normalisation.py:39-68 through layers.conv2D: no gamma / beta, axes (1, 2, 3); csrc/layer_norm.hip) ----
  * Per sample b over all N = H W C contiguous values of y [B][N]:

@@ -19,6 +19,7 @@ import math
 import numpy as np
 
 from phiseg_code_amd import many_class
+from phiseg_code_amd import multichannel
 from phiseg_code_amd import philox_host
 
 ROTATE, SCALE, FLIPLR, FLIPUD, ELASTIC = 1, 2, 4, 8, 16
@@ -95,7 +96,7 @@ def pack_params(decisions, src_indices, annotators, X, Y, ctrl=None):
 
 class DeviceBatchProvider:
     """BatchProvider (data/batch_provider.py:19-67) over arrays resident in HBM.  X [N, X, Y] float32 (images - 0.5, never
-    re-normalised: lidc_data_loader.py:92), y [N, X, Y, A] uint8."""
+    re-normalised: lidc_data_loader.py:92) or [N, X, Y, Cx] with 1 <= Cx <= 16 channels, y [N, X, Y, A] uint8."""
 
     def __init__(self, X, y, indices=None, do_augmentations=False, augmentation_options=None, num_labels_per_subject=1,
                  annotator_range=None, seed=1234, nlabels=2, **kwargs):
@@ -104,8 +105,11 @@ class DeviceBatchProvider:
         self.L = rt.lib()
         assert self.L.augment_param_bytes() == PARAM_DTYPE.itemsize
         X = np.asarray(X, dtype=np.float32)
-        if X.ndim == 4:
+        self.channels = 1
+        if X.ndim == 4 and X.shape[3] == 1:
             X = X[..., 0]
+        elif X.ndim == 4:                                            # a multi-channel data set is kept whole, [N, X, Y, Cx] (multichannel.py)
+            self.channels = multichannel.check_channels(X.shape[3], "the channel axis of X")
         y = np.asarray(y, dtype=np.uint8)
         if y.ndim == 3:
             y = y[..., None]
@@ -114,7 +118,7 @@ class DeviceBatchProvider:
         dev = torch.device("cuda", torch.cuda.current_device())
         self.images_dev = torch.as_tensor(np.ascontiguousarray(X)).to(dev)
         self.labels_dev = torch.as_tensor(np.ascontiguousarray(y)).to(dev)
-        self.images, self.labels = X[..., None], y                  # host views (validation reads .images / .labels)
+        self.images, self.labels = (X[..., None] if self.channels == 1 else X), y      # host views (validation reads .images / .labels)
         self.indices = np.arange(X.shape[0]) if indices is None else np.asarray(indices)
         self.unused_indices = self.indices.copy()
         self.do_augmentations = do_augmentations
@@ -157,14 +161,23 @@ class DeviceBatchProvider:
         if x_ptr is None:
             key = batch_size
             if key not in self._out:
-                self._out[key] = (torch.empty(batch_size, Xs, Ys, 1, dtype=torch.float32, device=par.device),
+                self._out[key] = (torch.empty(batch_size, Xs, Ys, self.channels, dtype=torch.float32, device=par.device),
                                   torch.empty(batch_size, Xs, Ys, dtype=torch.uint8, device=par.device))
             xo, so = self._out[key]
             x_ptr, s_ptr = xo.data_ptr(), so.data_ptr()
         else:
             xo = so = None
         st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        if many_class.label_route(self.nlabels) == "nearest":        # more than four labels: nearest-neighbour label maps, plain or elastic
+        if multichannel.augment_entry(self.channels, self.nlabels, ctrl is not None) == "augment_batch_mc":
+            key = ("mc", batch_size)                                 # more than one image channel: one entry, every label route, plain or elastic
+            if key not in self._ws:
+                nb = self.L.augment_batch_mc_ws_bytes(batch_size, Xs, Ys, self.channels, self.nlabels, 1 if ctrl is not None else 0)
+                self._ws[key] = (torch.empty(nb, dtype=torch.uint8, device=par.device) if nb else None, nb)
+            ws, nb = self._ws[key]
+            self.L.augment_batch_mc(self.images_dev.data_ptr(), self.labels_dev.data_ptr(), par.data_ptr(),
+                                    par.data_ptr() + rec.nbytes if ctrl is not None else None, x_ptr, s_ptr,
+                                    ws.data_ptr() if nb else None, nb, batch_size, Xs, Ys, self.n_annot, self.channels, self.nlabels, st)
+        elif many_class.label_route(self.nlabels) == "nearest":      # more than four labels: nearest-neighbour label maps, plain or elastic
             key = ("nearest", batch_size)
             if key not in self._ws:
                 nb = self.L.augment_batch_nearest_ws_bytes(batch_size, Xs, Ys, 1 if ctrl is not None else 0)
@@ -188,7 +201,7 @@ class DeviceBatchProvider:
         return xo, so
 
     def next_batch(self, batch_size):
-        """The reference's call (phiseg_model.py:193): host arrays x [B, X, Y, 1] float32, s [B, X, Y] uint8."""
+        """The reference's call (phiseg_model.py:193): host arrays x [B, X, Y, Cx] float32, s [B, X, Y] uint8."""
         import torch
         xo, so = self.next_batch_device(batch_size)
         torch.cuda.synchronize()

@@ -9,7 +9,8 @@ class BatchProvider(DeviceBatchProvider):
 
     def __init__(self, X, y, indices, add_dummy_dimension=True, do_augmentations=False, augmentation_options=None,
                  num_labels_per_subject=1, annotator_range=None, **kwargs):
-        if not add_dummy_dimension:
-            raise NotImplementedError("add_dummy_dimension=False: every call site of the reference passes True (lidc_data.py:36-50)")
+        import numpy as np
+        if not add_dummy_dimension and np.ndim(X) != 4:      # the reference's meaning of the flag: X already carries its channel axis
+            raise ValueError("add_dummy_dimension=False: X is [N, X, Y, channels], got %d dimensions" % np.ndim(X))
         super().__init__(X, y, indices=indices, do_augmentations=do_augmentations, augmentation_options=augmentation_options,
                          num_labels_per_subject=num_labels_per_subject, annotator_range=annotator_range, **kwargs)

@@ -9,6 +9,7 @@ import torch
 
 from phiseg_code_amd import graph as G
 from phiseg_code_amd import many_class
+from phiseg_code_amd import multichannel
 from phiseg_code_amd import runtime as rt
 from phiseg_code_amd import upconv
 from phiseg_code_amd.tfwrapper import normalisation as tfnorm
@@ -141,8 +142,12 @@ class ForwardLowering:
         if b.op.type == "sub_const" and b.op.inputs[0].op.type == "one_hot":
             # concat[x, one_hot(s) - 0.5] (posteriors.py:87) in one kernel
             oh = b.op.inputs[0].op
-            assert abs(b.op.attrs["c"] - 0.5) < 1e-12 and a.shape[-1] == 1
             xb, sb = self.val[a], self.val[oh.inputs[0]]
+            if a.shape[-1] > 1:                # a multi-channel image (multichannel.py): the entry of its own, Cx = 1 keeps the one below
+                assert abs(b.op.attrs["c"] - 0.5) < 1e-12 and multichannel.posterior_input_entry(a.shape[-1]) == "posterior_input_mc"
+                self._emit(self.L.posterior_input_mc, xb.ptr, sb.ptr, out.ptr, out.dt, npix, a.shape[-1], oh.attrs["depth"], self.stream)
+                return
+            assert abs(b.op.attrs["c"] - 0.5) < 1e-12 and a.shape[-1] == 1
             self._emit(self.L.posterior_input, xb.ptr, sb.ptr, out.ptr, out.dt, npix, oh.attrs["depth"], self.stream)
             return
         ab, bb = self._as_dt(self.val[a], out.dt), self._as_dt(self.val[b], out.dt)

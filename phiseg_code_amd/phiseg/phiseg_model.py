@@ -23,6 +23,7 @@ import numpy as np
 from phiseg_code_amd import engine
 from phiseg_code_amd import graph as G
 from phiseg_code_amd import many_class
+from phiseg_code_amd import multichannel
 from phiseg_code_amd import optimizers
 from phiseg_code_amd import utils
 from phiseg_code_amd.tfwrapper import normalisation as tfnorm
@@ -263,6 +264,8 @@ class phiseg():
     def checks(self):
         # the label maps are uint8 and the class-aware kernels stop at 256 classes: say so here, not from inside the first launch
         many_class.check_nlabels(self.exp_config.nlabels)
+        # likewise the image channels: 1 .. 16 (multichannel.py)
+        multichannel.check_image_size(self.exp_config.image_size)
 
     def add_loss_term(self, name, scalar, weight=1.0):
         """Add a scalar of the caller's making (tfwrapper.losses.dice_loss, cross_entropy_loss, ... on a tensor of this model) to the
@@ -467,7 +470,7 @@ class phiseg():
             B = int(np.asarray(x_b).shape[0])
             xb, sb = plan.feeds['x_input'], plan.feeds['s_input']
             H, W = xb.shape[1], xb.shape[2]
-            grids.append(('x_inp', summary.grid_u8_device(xb.ptr, summary.GRID_IMAGE_F32, B, H, W, 1, stream)))
+            grids.append(('x_inp', summary.grid_image_device(xb.ptr, B, H, W, xb.shape[3], stream)))
             grids.append(('s_inp', summary.grid_u8_device(sb.ptr, summary.GRID_LABELS_U8, B, H, W, 1, stream)))
             for name, t in spec['images']:
                 b = plan.val[t]
@@ -522,7 +525,7 @@ class phiseg():
             xb = plan.feeds['x_input']
             H, W = xb.shape[1], xb.shape[2]
             seg = S.grid_u8_device(lg.ptr, S.GRID_LOGITS_F32, B, H, W, lg.shape[-1], plan.stream, shift=lg.shift)
-            xin = S.grid_u8_device(xb.ptr, S.GRID_IMAGE_F32, B, H, W, 1, plan.stream)
+            xin = S.grid_image_device(xb.ptr, B, H, W, xb.shape[3], plan.stream)
             plan.sync()
             values += [S.image_value('generated_seg/image/0', seg.cpu().numpy()), S.image_value('generated_x_in/image/0', xin.cpu().numpy())]
             self._advance_noise()

@@ -87,7 +87,7 @@ class _Lib:
                         "phx_conv3x3_f32_mfma_supported", "phx_conv3x3_f32_mfma_packed_floats", "phx_conv3x3_f32_mfma_wgrad_supported",
                         "phx_conv3x3_f32_mfma_wgrad_ws_bytes", "phx_bn_bwd_onepass_supported", "phx_bn_bwd_onepass_barrier_words",
                         "phx_renorm_small_supported", "phx_renorm_tail_desc_bytes", "phx_layer_norm_one_launch_max", "phx_layer_norm_ws_floats",
-                        "phx_residual_ce_wide_ws_bytes", "phx_metrics_wide_ws_bytes", "phx_augment_batch_nearest_ws_bytes",
+                        "phx_residual_ce_wide_ws_bytes", "phx_metrics_wide_ws_bytes", "phx_augment_batch_nearest_ws_bytes", "phx_augment_batch_mc_ws_bytes",
                         "phx_conv2d_pad_wgrad_ws_floats"):
                 if name.endswith("_ws_bytes") or name.endswith("_packed_floats") or name.endswith("_ws_floats"):
                     fn.restype = ctypes.c_size_t

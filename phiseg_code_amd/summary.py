@@ -91,16 +91,40 @@ def png_encode_gray8(img):
             chunk(b"IDAT", zlib.compress(raw.tobytes(), 1)) + chunk(b"IEND", b""))
 
 
+def png_encode(img):
+    """[H, W] / [H, W, 1] (greyscale, colour type 0), [H, W, 3] (RGB, type 2) or [H, W, 4] (RGBA, type 6) uint8 -> PNG bytes; the
+    writer of png_encode_gray8 (filter 0 on every row, one IDAT chunk, compression level 1)."""
+    a = np.ascontiguousarray(img, dtype=np.uint8)
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    if a.ndim == 2:
+        return png_encode_gray8(a)
+    if a.ndim != 3 or a.shape[2] not in (3, 4) or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("png_encode: a non-empty [H, W], [H, W, 3] or [H, W, 4] image, got shape %s" % (a.shape,))
+    h, w, c = a.shape
+    raw = np.zeros((h, w * c + 1), dtype=np.uint8)      # a filter-type byte (0 = none) in front of every scanline
+    raw[:, 1:] = a.reshape(h, w * c)
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xffffffff)
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2 if c == 3 else 6, 0, 0, 0)) +
+            chunk(b"IDAT", zlib.compress(raw.tobytes(), 1)) + chunk(b"IEND", b""))
+
+
 def scalar_value(tag, value):
     """-> encoded Summary.Value {tag, simple_value}"""
     return _bytes_field(1, tag.encode()) + _key(2, 5) + struct.pack("<f", float(value))
 
 
 def image_value(tag, img):
-    """[H, W] uint8 -> encoded Summary.Value {tag, image {height, width, colorspace 1 (greyscale), PNG}}"""
+    """[H, W] uint8 -> encoded Summary.Value {tag, image {height, width, colorspace 1 (greyscale), PNG}}; [H, W, 3] / [H, W, 4]:
+    colorspace 3 (RGB) / 4 (RGBA)"""
     a = np.asarray(img)
-    png = png_encode_gray8(a)
-    im = _key(1, 0) + put_varint(a.shape[0]) + _key(2, 0) + put_varint(a.shape[1]) + _key(3, 0) + put_varint(1) + _bytes_field(4, png)
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    png = png_encode_gray8(a) if a.ndim == 2 else png_encode(a)
+    cs = 1 if a.ndim == 2 else a.shape[2]
+    im = _key(1, 0) + put_varint(a.shape[0]) + _key(2, 0) + put_varint(a.shape[1]) + _key(3, 0) + put_varint(cs) + _bytes_field(4, png)
     return _bytes_field(1, tag.encode()) + _bytes_field(4, im)
 
 
@@ -301,6 +325,26 @@ def grid_u8_device(ptr, form, B, H, W, C, stream, shift=0):
     work = torch.empty(8, dtype=torch.uint8, device=dev)
     rt.lib().summary_grid_u8(ptr, form, B, H, W, C, shift, gy, gx, out.data_ptr(), work.data_ptr(), stream)
     out._phx_work = work                                   # (keeps the scratch alive until the grid is read)
+    return out
+
+
+def grid_image_device(ptr, B, H, W, Cx, stream):
+    """The grid of an image batch [B, H, W, Cx] f32 on the device (NOT synchronised): Cx = 1 is grid_u8_device(GRID_IMAGE_F32); above,
+    phx_summary_grid_image_mc -> uint8 [(H + 2) * grid_Y, (W + 2) * grid_X, Cout] with Cout = multichannel.summary_channels(Cx), the
+    last axis dropped where it is 1 (channel 0 in grey)."""
+    import torch
+    from . import multichannel
+    from . import runtime as rt
+    if multichannel.summary_grid_entry(Cx) == "summary_grid_u8":
+        return grid_u8_device(ptr, GRID_IMAGE_F32, B, H, W, 1, stream)
+    cout = multichannel.summary_channels(Cx)
+    gy, gx = factorization(B)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    out = torch.empty((H + 2) * gy, (W + 2) * gx, cout, dtype=torch.uint8, device=dev)
+    work = torch.empty(8, dtype=torch.uint8, device=dev)
+    rt.lib().summary_grid_image_mc(ptr, B, H, W, Cx, cout, gy, gx, out.data_ptr(), work.data_ptr(), stream)
+    out = out[:, :, 0] if cout == 1 else out
+    out._phx_work = work
     return out
 
 
